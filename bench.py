@@ -17,11 +17,17 @@ Multi-GPU (torchrun, one process per GPU): weak scaling -- every rank runs its o
 requests (multi-start sharding has no data-path collective); timing is the max over ranks;
 value = all ranks' prices / that time.
 
-Also reported: the roofline of the request kernel (HIP events on its stream; frac = the fp64
-flops the hardware executed per request, from the committed rocprofv3 counter pass, over this
-run's request time), full calibrations of the same surface (calibrations/sec, both optimizer
-drivers) and a CPU baseline (the scalar-structured NumPy port in oracle/, timed on a bounded
-sample on rank 0, anchored to the reference by profiles/cpu_anchor.json).
+A plain run does only what the headline figure needs: set up, warm up, time the steps, write the
+outputs (--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy) and print the
+line.  The timed steps cycle through at most MAX_STEP_ROWS distinct param-set rows, so the setup
+does not grow with --steps.
+
+With --full also reported: the roofline of the request kernel (HIP events on its stream; frac =
+the fp64 flops the hardware executed per request, from the committed rocprofv3 counter pass, over
+this run's request time), the device/host spot check and the host-API rate, the side legs, full
+calibrations of the same surface (calibrations/sec, both optimizer drivers) and a CPU baseline
+(the scalar-structured NumPy port in oracle/, timed on a bounded sample on rank 0, anchored to the
+reference by profiles/cpu_anchor.json); --no-cpu / --no-calib / --no-side trim a --full run.
 """
 import argparse
 import json
@@ -363,6 +369,18 @@ def _max_over_ranks(dt, world, coll):
 
 
 PREWARM_S = 0.25          # untimed back-to-back requests before the warm-up steps (request_bench)
+MAX_STEP_ROWS = 256       # distinct param-set rows the timed steps cycle through (request_bench)
+MAX_WARM_ROWS = 64        # ... and the warm-up steps
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each array as path/<name>.npy (float64), 64 MB at most in all."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def event_ms(run, stream, reps):
@@ -377,10 +395,12 @@ def event_ms(run, stream, reps):
     return float(np.median([e0.elapsed_time(e1) for e0, e1 in evs]))
 
 
-def gen_batch(P, N, steps, warmup, dev, stream, rank, world=1, coll=None):
+def gen_batch(P, N, steps, warmup, dev, stream, rank, world=1, coll=None, full=True, dump=False):
     """C5 timing: one step = price every (param set, option) of a P-sample generator batch
-    (dh_surface_price_dev, strikes K_relative * spot / 100 formed on the device), after a
-    host/device spot check.  -> dict(value, ms_per_step, ker_ms, P, M, N, n_chunks, surf)."""
+    (dh_surface_price_dev, strikes K_relative * spot / 100 formed on the device).  full: a
+    host/device spot check first and the isolated HIP-event time (ker_ms) afterwards; dump: keep a
+    fixed seeded sample of the last step's prices (outputs).
+    -> dict(value, ms_per_step, ker_ms, P, M, N, n_chunks, surf, outputs)."""
     sptr = stream.cuda_stream
     Krel = np.tile(np.linspace(80.0, 120.0, 8), 4)
     T = np.repeat([0.25, 0.5, 1.0, 2.0], 8)
@@ -400,12 +420,13 @@ def gen_batch(P, N, steps, warmup, dev, stream, rank, world=1, coll=None):
         surf.price_dev(d_params.data_ptr(), P, d_out.data_ptr(), N=N, stream=sptr)
 
     # correctness spot check first, so that the warm-up passes run right ahead of the timed ones
-    run()
-    torch.cuda.synchronize()
-    chk = np.arange(0, P, max(1, P // 64))
-    got = d_out[torch.from_numpy(chk).to(dev)].cpu().numpy()
-    ref = surf.price(host[chk], N)          # a 64-set call: the large-tile kernel (last bits differ)
-    assert np.all(np.abs(got - ref) <= 1e-12 * np.abs(ref) + 1e-12), "device/host path mismatch"
+    if full:
+        run()
+        torch.cuda.synchronize()
+        chk = np.arange(0, P, max(1, P // 64))
+        got = d_out[torch.from_numpy(chk).to(dev)].cpu().numpy()
+        ref = surf.price(host[chk], N)      # a 64-set call: the large-tile kernel (last bits differ)
+        assert np.all(np.abs(got - ref) <= 1e-12 * np.abs(ref) + 1e-12), "device/host path mismatch"
     for _ in range(warmup):
         run()
     if world > 1:
@@ -416,7 +437,14 @@ def gen_batch(P, N, steps, warmup, dev, stream, rank, world=1, coll=None):
         run()
     torch.cuda.synchronize()
     dt = _max_over_ranks(time.perf_counter() - t0, world, coll)
-    ker_ms = event_ms(run, stream, max(3, min(steps, 10)))
+    outputs = None
+    if dump:
+        # every step prices the same batch; a fixed seeded sample of its rows (a quarter of the
+        # dump's bound: 63,550 of 1M) keeps the files small
+        n_rows = min(P, DUMP_MAX_BYTES // 4 // (8 * (M + 1)))
+        rows = np.sort(np.random.RandomState(0).choice(P, n_rows, replace=False))
+        outputs = {"prices": d_out[torch.from_numpy(rows).to(dev)].cpu().numpy(), "rows": rows}
+    ker_ms = event_ms(run, stream, max(3, min(steps, 10))) if full else None
     # launches per batch: the split path (--path split) chunks param sets so one chunk's tables
     # stay within 256 MiB (dh_kernels.hip launch_price: per set = groups x (N + 8 consts + clamp
     # words + largest group) doubles), the committed PMC bytes being per launch pair; the
@@ -427,7 +455,7 @@ def gen_batch(P, N, steps, warmup, dev, stream, rank, world=1, coll=None):
         n_chunks = 1
     return {"value": P * M * steps * world / dt, "ms_per_step": dt / steps * 1e3,
             "ker_ms": ker_ms, "P": P, "M": M, "N": N, "n_chunks": n_chunks, "surf": surf,
-            "steps": steps, "warmup": warmup}
+            "steps": steps, "warmup": warmup, "outputs": outputs}
 
 
 def gen_roofline(g, config):
@@ -447,23 +475,27 @@ def gen_roofline(g, config):
 
 def bench_generator(args, cfg, world, rank, dev, coll, stream, cpu=None):
     """--config c5: the generator batch as the headline line."""
-    g = gen_batch(cfg["P"], cfg["N"], args.steps, args.warmup, dev, stream, rank, world, coll)
+    g = gen_batch(cfg["P"], cfg["N"], args.steps, args.warmup, dev, stream, rank, world, coll,
+                  full=args.full, dump=bool(args.dump_outputs) and rank == 0)
+    if g["outputs"]:
+        dump_outputs(args.dump_outputs, g["outputs"])
     line = None
     if rank == 0:
         line = {"metric": "option-prices/sec (COS, generator batch)", "value": g["value"],
                 "unit": "option-prices/s", "n_gpus": world, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": g["ms_per_step"],
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-                "data": "synthetic",
+                "data": "synthetic", "full": args.full,
                 "config": {"workload": cfg["workload"], "param_sets": g["P"], "options": g["M"],
                            "cos_terms": g["N"], "prices_per_step": g["P"] * g["M"],
                            "tail_cut": args.tail_cut, "world_size_seen": world,
-                           "parallelism": f"independent batches per rank x{world}"},
-                "roofline": gen_roofline(g, args.config)}
+                           "parallelism": f"independent batches per rank x{world}"}}
+        if args.full:
+            line["roofline"] = gen_roofline(g, args.config)
         if cpu:
             line["cpu_baseline"] = cpu
             line["speedup_vs_cpu"] = g["value"] / cpu["value"]
-    e2e = None if args.no_calib else generator_end_to_end(world, rank, coll)
+    e2e = generator_end_to_end(world, rank, coll) if args.full and not args.no_calib else None
     if rank == 0:
         if e2e:
             line["generator_end_to_end"] = e2e
@@ -523,10 +555,13 @@ def generator_end_to_end(world, rank, coll, n_samples=1_000_000, host_path=False
     return r
 
 
-def request_bench(cfg, steps, warmup, world, rank, dev, coll, stream, starts_rank=None):
+def request_bench(cfg, steps, warmup, world, rank, dev, coll, stream, starts_rank=None,
+                  full=True, dump=False):
     """Function+gradient requests on cfg's surface: `steps` timed back to back after `warmup`,
-    each at different param sets (inputs resident in HBM), plus the median isolated request
-    (HIP events) and the PCIe-inclusive host-API rate.  -> dict."""
+    each at different param sets (inputs resident in HBM; the timed steps cycle through
+    min(steps, MAX_STEP_ROWS) rows, the warm-up steps through rows of their own).  full: also a
+    device/host spot check, the PCIe-inclusive host-API rate and the median isolated request (HIP
+    events); dump: keep what the last timed step wrote (outputs).  -> dict."""
     sptr = stream.cuda_stream
     opts, S0, r = make_surface(cfg["nK"], cfg["nT"], N=cfg["N"], put_itm=cfg["put_itm"])
     M = len(opts)
@@ -535,7 +570,8 @@ def request_bench(cfg, steps, warmup, world, rank, dev, coll, stream, starts_ran
     if starts_rank is None:
         starts_rank = cfg["starts"]
     S = 14 * starts_rank
-    n_rows = steps + max(warmup, 1)
+    n_timed = max(1, min(steps, MAX_STEP_ROWS))
+    n_rows = n_timed + max(1, min(warmup, MAX_WARM_ROWS))
     host = step_params(cal, n_rows, starts_rank, seed=100 + rank)
     d_params = torch.from_numpy(host).to(dev)
     d_sse = torch.empty((n_rows, S), dtype=torch.float64, device=dev)
@@ -545,27 +581,36 @@ def request_bench(cfg, steps, warmup, world, rank, dev, coll, stream, starts_ran
             for i in range(n_rows)]
     loss_dev = surf.loss_dev
 
-    def run(i):
-        pp, ps, pb = ptrs[i % n_rows]
+    timed_ptrs, warm_ptrs = ptrs[:n_timed], ptrs[n_timed:]
+    n_warm = len(warm_ptrs)
+
+    def run(i):                                   # timed step i
+        pp, ps, pb = timed_ptrs[i % n_timed]
         loss_dev(pp, S, ps, pb, N=N, stream=sptr)
 
-    # correctness spot check of one step against the host API (same kernel, host copies), before
-    # the warm-up so that the warm-up steps run right ahead of the timed ones; the context's
-    # scratch is shared, so the bench stream is drained around it
-    run(steps)
-    torch.cuda.synchronize()
-    sse_h, bad_h, _ = surf.loss_terms(host[steps], N)
-    assert np.array_equal(sse_h, d_sse[steps].cpu().numpy()), "device/host path mismatch"
-    # host-API rate (PCIe-inclusive: params H2D, losses D2H, synchronous) -- reported, not
-    # `value`.  Measured ahead of the warm-up: a few ms of requests that also bring the GPU from
-    # the idle of the CPU-baseline leg to its sustained clock before the W warm-up steps
+    def run_warm(i):                              # warm-up step i
+        pp, ps, pb = warm_ptrs[i % n_warm]
+        loss_dev(pp, S, ps, pb, N=N, stream=sptr)
+
     prices_per_step = S * M
-    n_host = max(5, min(steps, 50))
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(n_host):
-        surf.loss_terms(host[i % n_rows], N)
-    host_rate = prices_per_step * n_host / (time.perf_counter() - t0)
+    host_rate = None
+    if full:
+        # correctness spot check of one step against the host API (same kernel, host copies),
+        # before the warm-up so that the warm-up steps run right ahead of the timed ones; the
+        # context's scratch is shared, so the bench stream is drained around it
+        run_warm(0)
+        torch.cuda.synchronize()
+        sse_h, bad_h, _ = surf.loss_terms(host[n_timed], N)
+        assert np.array_equal(sse_h, d_sse[n_timed].cpu().numpy()), "device/host path mismatch"
+        # host-API rate (PCIe-inclusive: params H2D, losses D2H, synchronous) -- reported, not
+        # `value`.  Measured ahead of the warm-up: a few ms of requests that also bring the GPU
+        # from the idle of the CPU-baseline leg to its sustained clock before the W warm-up steps
+        n_host = max(5, min(steps, 50))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(n_host):
+            surf.loss_terms(host[i % n_rows], N)
+        host_rate = prices_per_step * n_host / (time.perf_counter() - t0)
     # then device requests back to back for PREWARM_S of wall time (untimed, before the W warm-up
     # steps): an idle MI355X takes tens of ms to reach its sustained clock, and a 20-step timed
     # region (~1.2 ms on C3) right after a few ms of work measured 63.8 us per step against
@@ -574,13 +619,13 @@ def request_bench(cfg, steps, warmup, world, rank, dev, coll, stream, starts_ran
     t0 = time.perf_counter()
     while time.perf_counter() - t0 < PREWARM_S:
         for _ in range(16):
-            run(steps + n_pre % max(warmup, 1))
+            run_warm(n_pre)
             n_pre += 1
         torch.cuda.synchronize()
 
     def timed(k):
         for i in range(warmup):
-            run(steps + i)
+            run_warm(i)
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -591,8 +636,12 @@ def request_bench(cfg, steps, warmup, world, rank, dev, coll, stream, starts_ran
         return _max_over_ranks(time.perf_counter() - t0, world, coll)
 
     dt = timed(steps)
-    ker_ms = event_ms(run, stream, max(20, min(steps, 200)))
-    return {"value": prices_per_step * steps * world / dt, "dt": dt,
+    outputs = None
+    if dump:                                      # before any later leg writes these rows again
+        last = (steps - 1) % n_timed
+        outputs = {"sse": d_sse[last].cpu().numpy(), "bad": d_bad[last].cpu().numpy()}
+    ker_ms = event_ms(run, stream, max(20, min(steps, 200))) if full else None
+    return {"value": prices_per_step * steps * world / dt, "dt": dt, "outputs": outputs,
             "ms_per_step": dt / steps * 1e3, "ker_ms": ker_ms, "S": S, "M": M, "N": N,
             "prices_per_step": prices_per_step, "opts": opts, "S0": S0, "r": r, "surf": surf,
             "host_rate": host_rate, "timed": timed, "run": run, "steps": steps,
@@ -749,10 +798,18 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-calib", action="store_true", help="skip the full-calibration leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: spot check, roofline "
+                         "(isolated HIP-event time), host-API rate, side legs, full "
+                         "calibrations, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; "
+                         "rank 0): sse and bad per param set, or (c5) prices of the sampled rows")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-calib", action="store_true",
+                    help="--full: skip the full-calibration leg")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the N = 1 side legs of the c3 line (tail cut off, C2 single "
+                    help="--full: skip the N = 1 side legs of the c3 line (tail cut off, C2 single "
                          "start, C5 generator batch)")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--path", default="auto", choices=["auto", "split", "fused"],
@@ -770,6 +827,8 @@ def main():
     cfg = CONFIGS[args.config]
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     # --gpus N launches its own N ranks when no launcher did (first, before anything touches
     # the GPU); under a launcher the world must be the one asked for
@@ -782,7 +841,7 @@ def main():
     # CPU baseline first, on rank 0 at N = 1 only, before anything initialises the GPU (its
     # process pool forks)
     cpu = None
-    if not args.no_cpu and rank == 0 and world == 1:
+    if args.full and not args.no_cpu and rank == 0 and world == 1:
         c_opts, c_S0, c_r = cpu_options(cfg)
         cpu = cpu_baseline(c_opts, c_S0, c_r, cfg["N"], args.cpu_budget, args.cpu_cores)
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -836,14 +895,17 @@ def main():
     # c4 deals its 64 starts over the ranks (strong scaling); the others run a fixed request per
     # rank (weak scaling)
     starts_rank = -(-cfg["starts"] // world) if cfg.get("strong") else cfg["starts"]
-    q = request_bench(cfg, args.steps, args.warmup, world, rank, dev, coll, stream, starts_rank)
-    roofline = request_roofline(q, args.config)
+    q = request_bench(cfg, args.steps, args.warmup, world, rank, dev, coll, stream, starts_rank,
+                      full=args.full, dump=bool(args.dump_outputs) and rank == 0)
+    if q["outputs"]:
+        dump_outputs(args.dump_outputs, q["outputs"])
+    roofline = request_roofline(q, args.config) if args.full else None
     opts, S0, r, N, M = q["opts"], q["S0"], q["r"], q["N"], q["M"]
 
     # side legs (N = 1, the default c3 line): what the cuts buy, configs[1] as stated (single
     # start), and the metric's own N = 128 (the generator batch)
     side = {}
-    if world == 1 and args.config == "c3" and not args.no_side:
+    if args.full and world == 1 and args.config == "c3" and not args.no_side:
         if args.tail_cut == "on":
             side["tail_cut_off"] = tail_cut_off_leg(q)
         side["c2_single_start"] = c2_single_start_leg(world, rank, dev, coll, stream,
@@ -854,7 +916,7 @@ def main():
             side["c1_calibration"] = c1_calibration_leg(world, coll)
     # the north star's two 8-GPU configurations, at every world size (N = 1 is their baseline):
     # C4's 64 starts sharded with the RCCL gather, C5's generator sharded end to end
-    if args.config == "c3" and not args.no_side and not args.no_calib:
+    if args.full and args.config == "c3" and not args.no_side and not args.no_calib:
         side["c4_sharded_64_starts"] = c4_sharded_leg(world, coll)
         if world > 1:
             side["c5_generator_sharded"] = generator_end_to_end(world, rank, coll)
@@ -865,7 +927,7 @@ def main():
     # reference's optimizer bit for bit, one launch + one host round trip per lockstep request)
     # and the device-resident L-BFGS-B (dh_calibrate_lbfgs) ----
     calib = calib_dev = None
-    if not args.no_calib:
+    if args.full and not args.no_calib:
         n_starts = cfg["starts"] if cfg.get("strong") else cfg["starts"] * world
         calib = calib_leg(S0, r, opts, N, n_starts, world, coll, "scipy")
         calib_dev = calib_leg(S0, r, opts, N, n_starts, world, coll, "device")
@@ -877,18 +939,19 @@ def main():
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": q["ms_per_step"],
             "higher_is_better": True,
             "scaling": "strong" if cfg.get("strong") else "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
+            "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": cfg["workload"], "options": M, "cos_terms": N,
                        "tail_cut": args.tail_cut, "param_sets_per_step": q["S"],
                        "prices_per_step": q["prices_per_step"], "world_size_seen": world_seen,
                        "backend": args.backend if world > 1 else None,
                        "parallelism": f"independent requests per rank x{world}"},
-            "roofline": roofline,
-            "host_api_prices_per_sec": q["host_rate"],
             "prewarm": {"seconds": PREWARM_S, "requests": q["prewarm_requests"],
                         "note": "untimed device requests before the warm-up steps, to the "
                                 "sustained clock"},
         }
+        if args.full:
+            line["roofline"] = roofline
+            line["host_api_prices_per_sec"] = q["host_rate"]
         line.update(side)
         if calib:
             line["calibration"] = calib

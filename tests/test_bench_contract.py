@@ -1,7 +1,8 @@
 """bench.py's output contract (the driver parses its last line): one JSON object with the metric
 and unit of BASELINE.json, the whole-job value, the timing fields, config.workload, the roofline
-object and -- on rank 0 at N = 1 -- the CPU baseline object.  Runs a short C1 bench on the GPU
-(a child process, as the driver runs it); the CPU baseline leg gets a 1 s budget."""
+object and -- with --full, on rank 0 at N = 1 -- the CPU baseline object.  Runs a short C1 bench on the
+GPU (a child process, as the driver runs it); the CPU baseline leg gets a 1 s budget.  A plain run
+(no --full) carries the headline fields only and writes its last step's outputs on request."""
 import json
 import os
 import subprocess
@@ -14,8 +15,8 @@ from conftest import ROOT
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "5",
-           "--warmup", "2", "--no-calib", "--cpu-budget", "1", "--cpu-cores", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "c1", "--steps",
+           "5", "--warmup", "2", "--no-calib", "--cpu-budget", "1", "--cpu-cores", "2"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=100)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -45,14 +46,48 @@ def test_bench_line_contract():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_last_step(tmp_path):
+    """Without --full the line holds the headline fields and none of the extra legs, --steps sets
+    the timed steps, and --dump-outputs writes what the last timed step computed: float64 arrays
+    that equal, bit for bit, the host API's losses at that step's (seeded) param sets."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c1",
+           "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=100)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["metric"].startswith("option-prices/sec") and line["unit"] == "option-prices/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["full"] is False
+    assert (line["n_gpus"], line["steps"], line["warmup"]) == (1, 7, 2)
+    per_step = line["config"]["prices_per_step"]
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - per_step) <= 1e-6 * per_step
+    for key in ("roofline", "cpu_baseline", "calibration", "calibration_device",
+                "host_api_prices_per_sec", "tail_cut_off", "c2_single_start"):
+        assert key not in line, key
+    got = {f: np.load(tmp_path / "out" / f) for f in sorted(os.listdir(tmp_path / "out"))}
+    assert sorted(got) == ["bad.npy", "sse.npy"]
+    assert all(a.dtype == np.float64 and a.shape == (14,) for a in got.values())
+    # the same inputs, rebuilt here: the 7th of the seeded rows, through the host API
+    import bench                      # conftest puts the repository root on sys.path
+    cfg = bench.CONFIGS["c1"]
+    opts, S0, r = bench.make_surface(cfg["nK"], cfg["nT"], N=cfg["N"], put_itm=cfg["put_itm"])
+    cal = bench.DoubleHestonJumpCalibrator(S0, r, opts, N=cfg["N"])
+    rows = bench.step_params(cal, 7 + 2, cfg["starts"], seed=100)
+    sse, bad, _ = cal._get_surface().loss_terms(rows[6], cfg["N"])
+    assert np.array_equal(got["sse.npy"], sse) and np.array_equal(got["bad.npy"], bad)
+    assert np.all(np.isfinite(sse)) and np.all(sse > 0)
+
+
+@pytest.mark.gpu
 def test_bench_line_contract_two_ranks():
     """The driver's N > 1 launch shape (torch.distributed.run, one JSON line from rank 0), rehearsed
     with two gloo ranks sharing the box's one GPU: n_gpus = 2, weak scaling, value = both ranks'
     prices per step / the max-over-ranks step time, no CPU-baseline leg at N > 1."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", "--master-port=29533", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--config", "c1", "--steps", "5", "--warmup", "2", "--no-calib",
-           "--backend", "gloo"]
+           "--gpus", "2", "--full", "--config", "c1", "--steps", "5", "--warmup", "2",
+           "--no-calib", "--backend", "gloo"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -116,8 +151,8 @@ def test_bench_side_legs_two_ranks():
     times), each reporting the world it saw."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", "--master-port=29541",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "c3", "--steps", "3",
-           "--warmup", "1", "--no-cpu", "--backend", "gloo"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--config", "c3", "--steps",
+           "3", "--warmup", "1", "--no-cpu", "--backend", "gloo"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -9,7 +9,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for v in ${VARIANTS:-base}; do
     envs=""; [ "$v" != base ] && envs=$(echo "$v" | tr ',' ' ')
     out=gpurun_out/ab/${CONFIG}_$(echo "$v" | tr '=,/.' '____')_$rep
-    timeout -k 10 150 env $envs python3 bench.py --config $CONFIG --no-cpu --no-calib --no-side \
+    timeout -k 10 150 env $envs python3 bench.py --full --config $CONFIG --no-cpu --no-calib --no-side \
         --steps ${STEPS:-200} --warmup 20 > $out.json 2> $out.err || { echo "$v failed"; tail -3 $out.err; exit 1; }
     python3 -c "
 import json; d=json.loads(open('$out.json').read().strip().splitlines()[-1])

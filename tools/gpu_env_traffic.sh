@@ -12,7 +12,7 @@ for v in ${VARIANTS:-base}; do
     g=$(echo $grp | cut -c1-12)
     export $envs
     timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $grp -d gpurun_out/prof -o ${tag}_${CONFIG}_$g --output-format csv \
-        -- python3 bench.py --config $CONFIG --steps 20 --warmup 3 --no-cpu --no-calib --no-side \
+        -- python3 bench.py --full --config $CONFIG --steps 20 --warmup 3 --no-cpu --no-calib --no-side \
         > gpurun_out/prof/${tag}_${CONFIG}_$g.log 2>&1 || { echo "pmc $v $g failed"; exit 1; }
     for e in $envs; do unset ${e%%=*}; done
     rm -f gpurun_out/prof/${tag}_${CONFIG}_${g}_kernel_trace.csv

@@ -8,7 +8,7 @@ for rep in 1 2; do
   for v in ${LIBS:-base}; do
     unset DHCOS_LIB
     [ "$v" != base ] && export DHCOS_LIB=$PWD/option-pricing-ffn-lbfgs_amd/dhcos/libdhcos_$v.so
-    timeout -k 10 120 python3 bench.py --config $CONFIG --path ${BPATH:-auto} --no-cpu --no-calib --no-side --steps ${STEPS:-200} --warmup 20 \
+    timeout -k 10 120 python3 bench.py --full --config $CONFIG --path ${BPATH:-auto} --no-cpu --no-calib --no-side --steps ${STEPS:-200} --warmup 20 \
         > gpurun_out/ab/${CONFIG}_${v}_$rep.json 2> gpurun_out/ab/${CONFIG}_${v}_$rep.err || { echo "$v failed"; tail -3 gpurun_out/ab/${CONFIG}_${v}_$rep.err; exit 1; }
     python3 -c "
 import json,sys; d=json.loads(open('gpurun_out/ab/${CONFIG}_${v}_$rep.json').read().strip().splitlines()[-1])

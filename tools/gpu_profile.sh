@@ -6,17 +6,17 @@
 #      FETCH_SIZE / WRITE_SIZE (separate passes, MI355X_MICROARCH.md), the fp64 instruction mix, and
 #      the L2's read requests by size (32 / 64 / 128 B: the fetched bytes exactly, for access widths
 #      the FETCH_SIZE x 2 correction is not calibrated for) and those that reached DRAM.
-# Outputs under gpurun_out/prof/; tools/summarize_profiles.py turns them into profiles/<TAG>_*.
+# Outputs under $OUT_ROOT/prof/; tools/summarize_profiles.py turns them into profiles/<TAG>_*.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 TAG=${TAG:-r01}
 CONFIGS=${CONFIGS:-"c2 c3 c5"}
-OUT=gpurun_out/prof
+OUT=${OUT_ROOT:-bench_out}/prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null || exit 1
 for c in $CONFIGS; do
   if [ $c = c5 ]; then STEPS="--steps 3 --warmup 1"; PSTEPS="--steps 1 --warmup 1"; else STEPS="--steps 100 --warmup 10"; PSTEPS="--steps 20 --warmup 3"; fi
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT -o ${TAG}_${c}_stats --output-format csv \
-      -- python bench.py --config $c $STEPS --no-cpu --no-calib --no-side \
+      -- python bench.py --full --config $c $STEPS --no-cpu --no-calib --no-side \
       > $OUT/${TAG}_${c}_stats.log 2>&1 || { echo "stats $c failed rc=$?"; exit 1; }
   echo "stats $c ok"
   i=0
@@ -24,7 +24,7 @@ for c in $CONFIGS; do
     [ -z "$grp" ] && continue
     i=$((i+1))
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc $grp -d $OUT -o ${TAG}_${c}_pmc$i --output-format csv \
-        -- python bench.py --config $c $PSTEPS --no-cpu --no-calib --no-side \
+        -- python bench.py --full --config $c $PSTEPS --no-cpu --no-calib --no-side \
         > $OUT/${TAG}_${c}_pmc$i.log 2>&1 || { echo "pmc $c pass $i failed rc=$?"; exit 1; }
     echo "pmc $c pass $i ($grp) ok"
   done <<EOG

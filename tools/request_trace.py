@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """The bench's timed requests out of a rocprofv3 kernel trace (rocprofv3 --kernel-trace
---output-format csv of `python bench.py --no-cpu --no-calib --steps K --warmup W`).
+--output-format csv of `python bench.py --full --no-cpu --no-calib --steps K --warmup W`).
 
-bench.py issues, on one stream and in this order, for the configured request shape:
+bench.py --full issues, on one stream and in this order, for the configured request shape:
   1 correctness-check request (device path), max(5, min(K, 50)) host-API requests (the same
   kernels), the pre-warm's requests (round 5: the line's prewarm.requests), W warm-up requests,
   K timed requests, then HIP-event-timed requests and the side legs.
