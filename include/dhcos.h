@@ -335,6 +335,35 @@ int dh_host_cache_trim(void);
 int dh_price_pairs(dh_ctx* ctx, const double* params, const double* K, const double* T,
                    const int8_t* is_call, int64_t P, int N, double L, double* out);
 
+/* ---- Black-Scholes implied volatility ----------------------------------------------------- */
+/* sigma[i] = the volatility whose Black-Scholes price of (S0[i], K[i], T[i], r[i], q[i],
+ * is_call[i]) is price[i]; every array has n entries (structure of arrays), one GPU lane per quote.
+ * Replaces nothing in the reference (it has no implied-vol code; its only trace is the
+ * implied_var start guess, lbfgs_calibrator.py:220-222): it replaces the per-option host
+ * root-finder a user of the price outputs runs.  With the bounds formed in fp64 as written,
+ *   call: lower = max(S0 e^{-qT} - K e^{-rT}, 0), upper = S0 e^{-qT}
+ *   put:  lower = max(K e^{-rT} - S0 e^{-qT}, 0), upper = K e^{-rT}
+ * the result is 0.0 where price == lower, and NaN where price < lower, price >= upper, price is
+ * not finite, S0 <= 0, K <= 0, T <= 0 or any input is NaN or infinite.  NaN is the only failure
+ * signal (a numeric failure is not an error).  Every quote is solved within a fixed number of
+ * steps whatever its value (csrc/dh_iv.h).
+ * Host pointers, synchronous; n == 0 is a no-op.                                               */
+int dh_implied_vol(dh_ctx* ctx, const double* price, const double* S0, const double* K,
+                   const double* T, const double* r, const double* q, const int8_t* is_call,
+                   int64_t n, double* sigma);
+/* The same over device pointers: one launch enqueued on `stream` (hipStream_t; NULL = the
+ * context's stream).  No synchronisation, no allocation.                                       */
+int dh_implied_vol_dev(dh_ctx* ctx, const double* d_price, const double* d_S0, const double* d_K,
+                       const double* d_T, const double* d_r, const double* d_q,
+                       const int8_t* d_is_call, int64_t n, double* d_sigma, void* stream);
+/* Model vols of a surface: prices it as dh_surface_price does (the same kernels, the same bits),
+ * then inverts every price on the device, without a host round trip: iv[p*M + m], m in the
+ * caller's original option order, from S0, r, q of param record p (slots 13..15) and K, T,
+ * is_call of option m (DH_STRIKE_PCT_SPOT: the strike K_relative * S0 / 100.0 the pricing forms).
+ * prices: optional [P][M] output of what dh_surface_price returns (NULL to skip).               */
+int dh_surface_implied_vol(dh_ctx* ctx, const dh_surface* s, const double* params, int64_t P,
+                           int N, double L, double* iv, double* prices);
+
 /* ---- building blocks (exposed for API parity with the reference's public methods) -------- */
 /* phi(u_j; tau) for one param set: DoubleHeston.characteristic_function (double_heston.py:48-97) */
 int dh_cf(dh_ctx* ctx, const double* params, const double* u, int n, double tau, double* re,

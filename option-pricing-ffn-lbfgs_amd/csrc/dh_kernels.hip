@@ -2886,6 +2886,7 @@ struct dh_ctx {
                                // the ticket hand-off (0); -1: not read yet
     std::vector<std::pair<std::array<int64_t, 3>, int>> resident_fused;
     GenBufs* gen = nullptr;    // the generator's device draw (dh_gen_device)
+    DevBuf iv;                 // quote columns / vols of dh_implied_vol, dh_surface_implied_vol
 };
 
 struct dh_surface {
@@ -3432,7 +3433,7 @@ int dh_ctx_destroy(dh_ctx* ctx) {
                       &ctx->consts, &ctx->cl_mask, &ctx->cl_price, &ctx->aux0,
                       &ctx->aux1, &ctx->aux2, &ctx->aux3, &ctx->pre, &ctx->lb_state, &ctx->lb_rec,
                       &ctx->lb_sse, &ctx->lb_bad, &ctx->lb_live, &ctx->lb_done, &ctx->lb_x0,
-                      &ctx->lb_trace, &ctx->lb_trace_n})
+                      &ctx->lb_trace, &ctx->lb_trace_n, &ctx->iv})
         b->release();
     ctx->h_params.release();
     ctx->h_loss.release();
@@ -5159,3 +5160,4 @@ extern "C" int dh_allgather_best(dh_comm* c, const double* rec, int rows, int wi
 }
 
 #include "dh_gen_device.h"
+#include "dh_iv.h"

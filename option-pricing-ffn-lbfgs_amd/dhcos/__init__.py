@@ -6,6 +6,7 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
     DoubleHestonJumpCalibrator,       src/calibration/lbfgs_calibrator.py
     CalibrationResult
     generate_synthetic_calibrations   src/data/synthetic_generator.py
+    implied_vol                       (new: Black-Scholes implied volatility of prices)
 
 All pricing arithmetic runs in libdhcos.so (hand-written gfx950 HIP kernels, C-ABI in
 include/dhcos.h); the native library is loaded on first use and there is no CPU fallback.
@@ -13,11 +14,11 @@ The reference's module names (double_heston, lbfgs_calibrator, synthetic_generat
 this package as one-line re-exports, and ``dhcos.distributed`` (import it explicitly; it needs
 torch) shards starts / samples over ``torch.distributed`` ranks (one process per GPU).
 """
-from .pricer import DoubleHeston
+from .pricer import DoubleHeston, implied_vol
 from .calibrator import CalibrationResult, DoubleHestonJumpCalibrator
 from .generator import generate_synthetic_calibrations
 from ._native import NativeError
 
 __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
-           "generate_synthetic_calibrations", "NativeError"]
+           "generate_synthetic_calibrations", "implied_vol", "NativeError"]
 __version__ = "0.1.0"

@@ -118,6 +118,10 @@ SIGNATURES = {
     "dh_surface_fg_end": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "dh_surface_fg_cancel": (C.c_int, [_vp, C.c_int]),
     "dh_price_pairs": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_double, _vp]),
+    "dh_implied_vol": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    "dh_implied_vol_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
+    "dh_surface_implied_vol": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_double, _vp,
+                                         _vp]),
     "dh_cf": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, _dp, _dp]),
     "dh_cf_complex": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp]),
     "dh_trunc_range": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int64, C.c_double, _dp, _dp]),
@@ -358,6 +362,47 @@ class Context:
                                          out.ctypes.data))
         return out[0]
 
+    def implied_vol(self, price, S0, K, T, r, q, is_call):
+        """dh_implied_vol: Black-Scholes implied vols of n quotes, every argument an array of n
+        (float64; is_call int8 / bool) -> sigma [n] (NaN where no vol exists, include/dhcos.h)."""
+        cols = [_f64(a).reshape(-1) for a in (price, S0, K, T, r, q)]
+        n = cols[0].size
+        ic = np.ascontiguousarray(is_call, dtype=np.int8).reshape(-1)
+        if any(c.size != n for c in cols) or ic.size != n:
+            raise ValueError("implied_vol: every argument must have the same length")
+        out = np.empty(n)
+        with self._lock:
+            _check(load().dh_implied_vol(self._h, *(c.ctypes.data if n else None for c in cols),
+                                         ic.ctypes.data if n else None, n,
+                                         out.ctypes.data if n else None))
+        return out
+
+    def implied_vol_dev(self, price, S0, K, T, r, q, is_call, out=None, stream=None):
+        """dh_implied_vol_dev over torch tensors on this context's device: float64 price, S0, K,
+        T, r, q and int8 is_call, contiguous, all of n elements -> sigma (``out`` or a new
+        float64 tensor).  One launch enqueued on ``stream`` -- a non-default torch stream or a raw
+        hipStream_t; None: the context's own stream, as the other _dev wrappers (then order it
+        against torch's work with ``synchronize()``) -- without synchronisation.  torch's default
+        stream has the null handle, which the C-ABI reads as the context's stream: it is refused."""
+        import torch
+        cols = (price, S0, K, T, r, q)
+        n = price.numel()
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=price.device)
+        for t, dt in [(c, torch.float64) for c in cols + (out,)] + [(is_call, torch.int8)]:
+            if (t.dtype != dt or not t.is_contiguous() or t.numel() != n or not t.is_cuda
+                    or t.device.index != self.device):
+                raise ValueError(f"implied_vol_dev: contiguous {dt} tensors of {n} elements on "
+                                 f"cuda:{self.device}")
+        st = 0 if stream is None else int(getattr(stream, "cuda_stream", stream))
+        if stream is not None and st == 0:
+            raise ValueError("implied_vol_dev: the default (null) stream cannot be named; pass a "
+                             "non-default stream, or None for the context's stream")
+        _check(load().dh_implied_vol_dev(self._h, *(_vp(c.data_ptr()) for c in cols),
+                                         _vp(is_call.data_ptr()), n, _vp(out.data_ptr()),
+                                         _vp(st) if st else None))
+        return out
+
     def cf(self, params16, u, tau):
         p = _f64(params16).reshape(PARAM_STRIDE)
         u = _f64(u).reshape(-1)
@@ -541,6 +586,20 @@ class Surface:
                                             g.ctypes.data, low.ctypes.data))
             self.ctx._fg_s[int(slot)] = None
         return f, g, low
+
+    def implied_vol(self, params, N=128, L=10.0, want_prices=False):
+        """dh_surface_implied_vol: the Black-Scholes vols [P, M] of the model prices of every
+        param row (S0, r, q from the row), inverted on the device; with want_prices also the
+        prices [P, M] (dh_surface_price's bits) -> iv or (iv, prices)."""
+        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        P = params.shape[0]
+        iv = np.empty((P, self.M))
+        prices = np.empty((P, self.M)) if want_prices else None
+        with self.ctx._lock:
+            _check(load().dh_surface_implied_vol(self.ctx.handle, self._h, params.ctypes.data, P,
+                                                 int(N), float(L), iv.ctypes.data,
+                                                 None if prices is None else prices.ctypes.data))
+        return (iv, prices) if want_prices else iv
 
     # device-pointer variants (torch tensors or raw device addresses)
     def price_dev(self, d_params: int, P: int, d_out: int, N=128, L=10.0, stream: int = 0):

@@ -248,13 +248,29 @@ def price_grid(params, spots, N=128, strikes=STRIKES_PCT, maturities=MATURITIES,
 def generate_synthetic_calibrations(n_samples: int = 500,
                                     save_path: str = "lbfgs_calibrations_synthetic.pkl", *,
                                     N: int = 128, device=None, as_arrays: bool = False,
-                                    verbose: bool = True, draw: str = "device"):
+                                    verbose: bool = True, draw: str = "device",
+                                    implied_vols: bool = False):
     """Generate ``n_samples`` synthetic calibrations (synthetic_generator.py:25-234).  By default
     the draws, recursions, pricing and assembly run on the device behind the host's serial walk of
     the RNG stream (generate_device); ``draw="host"``: the native host draw on a worker thread,
-    each chunk priced on the GPU as soon as the draw has finished it."""
+    each chunk priced on the GPU as soon as the draw has finished it.
+
+    ``implied_vols=True`` (with ``as_arrays=True`` only: the pickled records stay the
+    reference's) adds the columns ``market_iv`` and ``model_iv`` [n, 15]: the Black-Scholes
+    implied vols of ``market_prices`` and ``model_prices`` (one dh_implied_vol call each; NaN
+    where a noisy market price has none).  Every other key keeps its bits."""
     if draw not in ("device", "host"):
         raise ValueError("draw must be 'device' or 'host'")
+    if implied_vols and not as_arrays:
+        raise ValueError("implied_vols=True needs as_arrays=True")
+    if implied_vols:
+        # the columns are formed over the returned arrays, so the file is written after them
+        out = generate_synthetic_calibrations(n_samples, None, N=N, device=device, as_arrays=True,
+                                              verbose=verbose, draw=draw)
+        add_implied_vols(out, device=device)
+        if save_path:
+            save_arrays(out, save_path)
+        return out
     if draw == "device" and int(n_samples) > 0:
         o = generate_device(n_samples, N=N, device=device)
         return assemble(o["params"], o["spots"], None, o["model"], save_path, as_arrays=as_arrays,
@@ -300,6 +316,26 @@ def generate_synthetic_calibrations(n_samples: int = 500,
                     verbose=verbose, N=N, assembled=asm, dates=dates[0] if dates else None)
 
 
+def save_arrays(result, save_path):
+    """The columnar output as an .npz (param_names as an array)."""
+    np.savez(save_path if save_path.endswith(".npz") else save_path + ".npz",
+             **{k: v for k, v in result.items() if k != "param_names"},
+             param_names=np.array(result["param_names"]))
+
+
+def add_implied_vols(result, device=None):
+    """Adds ``market_iv`` and ``model_iv`` [n, m] to a columnar result: the Black-Scholes implied
+    vols of its market and model prices (calls, q = 0, the result's spots, strikes, maturities
+    and rate), one dh_implied_vol call each."""
+    from .pricer import implied_vol
+    spot = np.asarray(result["spot"])[:, None]
+    for name in ("market", "model"):
+        result[name + "_iv"] = implied_vol(result[name + "_prices"], spot, result["strikes"],
+                                           result["maturities"], result["risk_free"], 0.0, "C",
+                                           device=device)
+    return result
+
+
 def assemble(params, spots, noise, model, save_path, *, as_arrays=False, verbose=True, N=128,
              assembled=None, dates=None):
     """Host part after pricing: noise, per-sample loss, output records (:141-183)."""
@@ -328,9 +364,7 @@ def assemble(params, spots, noise, model, save_path, *, as_arrays=False, verbose
                       param_names=names, market_prices=market, model_prices=model,
                       strikes=strikes, maturities=Tg, final_loss=losses)
         if save_path:
-            np.savez(save_path if save_path.endswith(".npz") else save_path + ".npz",
-                     **{k: v for k, v in result.items() if k != "param_names"},
-                     param_names=np.array(names))
+            save_arrays(result, save_path)
         return result
     calibrations = []
     for i in range(n_samples):

@@ -32,6 +32,38 @@ def param_record(model13, S0, r, q=0.0) -> np.ndarray:
     return rec
 
 
+def _is_call_array(option_type) -> np.ndarray:
+    """price_batch's option_type rule: a string (reference rule), or a sequence / array of
+    strings (reference rule each) or booleans (is_call) -> a bool array (0-d for a string)."""
+    if isinstance(option_type, str):
+        return np.array(resolve_call(option_type))
+    ot = np.asarray(option_type)
+    if ot.dtype.kind in "US":
+        flat = [resolve_call(str(o)) for o in ot.reshape(-1)]
+        return np.array(flat, dtype=bool).reshape(ot.shape)
+    if ot.dtype.kind == "O":
+        flat = [resolve_call(o) if isinstance(o, str) else bool(o) for o in ot.reshape(-1)]
+        return np.array(flat, dtype=bool).reshape(ot.shape)
+    return ot.astype(bool)
+
+
+def implied_vol(price, S0, K, T, r, q=0.0, option_type="C", device=None):
+    """Black-Scholes implied volatility on the GPU (dh_implied_vol): the sigma whose price of a
+    European option (spot S0, strike K, maturity T, rate r, dividend yield q) is ``price``.
+
+    All arguments broadcast (NumPy rules); option_type as in ``DoubleHeston.price_batch``.
+    Returns an array of the broadcast shape, or an ``np.float64`` when every argument is a
+    scalar.  0.0 where the price equals its lower bound; NaN where no volatility exists (price
+    outside [lower, upper), non-finite or non-positive inputs) -- include/dhcos.h."""
+    ic = _is_call_array(option_type)
+    cols = [np.asarray(a, dtype=np.float64) for a in (price, S0, K, T, r, q)]
+    shape = np.broadcast_shapes(ic.shape, *(c.shape for c in cols))
+    flat = [np.ascontiguousarray(np.broadcast_to(c, shape)).reshape(-1) for c in cols]
+    icf = np.ascontiguousarray(np.broadcast_to(ic, shape), dtype=np.int8).reshape(-1)
+    out = _native.default_context(device).implied_vol(*flat, icf)
+    return out.reshape(shape) if shape else np.float64(out[0])
+
+
 class DoubleHeston:
     """Double Heston + lognormal (Merton) jumps, European call/put by the COS method."""
 
@@ -87,6 +119,12 @@ class DoubleHeston:
         return np.float64(self._ctx().price_one(self._record(), float(self.K), float(self.T),
                                                 is_call, N))
 
+    def implied_vol(self, N=128):
+        """The Black-Scholes implied volatility of ``pricing(N)`` (NaN where the model price has
+        none, e.g. below intrinsic)."""
+        return implied_vol(self.pricing(N), self.S0, self.K, self.T, self.r, self.q,
+                           self.option_type, device=self.device)
+
     # -- batched entry point ----------------------------------------------------------------
     @staticmethod
     def price_batch(params, S0, K, T, r, option_type="C", N=128, q=0.0, L=10.0, device=None):
@@ -112,3 +150,14 @@ class DoubleHeston:
         Kb = np.broadcast_to(np.asarray(K, dtype=np.float64), (n,))
         Tb = np.broadcast_to(np.asarray(T, dtype=np.float64), (n,))
         return _native.default_context(device).price_pairs(rec, Kb, Tb, ic, N, L)
+
+    @staticmethod
+    def implied_vol_batch(params, S0, K, T, r, option_type="C", N=128, q=0.0, L=10.0,
+                          device=None):
+        """``price_batch``'s arguments -> the Black-Scholes implied vols of its prices (option i
+        under param set i; the prices stay price_batch's bits)."""
+        prices = DoubleHeston.price_batch(params, S0, K, T, r, option_type, N, q, L, device)
+        n = prices.size
+        bc = [np.broadcast_to(np.asarray(a, dtype=np.float64), (n,)) for a in (S0, K, T, r, q)]
+        ic = _is_call_array(option_type)
+        return implied_vol(prices, *bc, option_type=np.broadcast_to(ic, (n,)), device=device)
