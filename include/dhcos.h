@@ -322,6 +322,18 @@ int dh_gen_device(dh_ctx* ctx, const dh_surface* grid, uint32_t* mt_key, int32_t
 /* The device's restatement of glibc's log (the legacy gauss's, dh_gen_device) over x[n]: its
  * GPU test against libm.                                                                         */
 int dh_gen_log(dh_ctx* ctx, const double* x, int64_t n, double* out);
+/* Test support: one of the fp64 elementary functions of csrc/dh_device.h over arrays, one GPU lane
+ * per element, for its test against a high-precision truth (csrc/dh_math_probe.h, which also fixes
+ * the layout; tests/test_gpu_math.py).  fn: 0 dsincos, 1 dsincos_t, 2 dexp, 3 dexp_nonpos,
+ * 4 dexp_t, 5 dexp_t_nonpos, 6 dlog, 7 dlog_t, 8 datan2, 9 datan2_t, 10 drcp, 11 dsqrt_rsqrt,
+ * 12 dsqrt_rsqrt_pos, 13 csqrt_p, 14 cdiv, 15 cdiv_rcp; any other value gives DH_E_ARG.
+ * x[n]: the argument, the first argument of atan2(y, x) (its "y"), or the real part; y[n]: the
+ * second argument or the imaginary part (not read by the one-argument functions, may be NULL).
+ * cdiv and cdiv_rcp read x[2n], y[2n]: the numerator x[i] + i y[i], the divisor x[n+i] + i y[n+i].
+ * out0[n], out1[n]: sin / cos, sqrt / rsqrt, re / im; a single result in out0 (out1 = 0).
+ * Host pointers, synchronous; n == 0 is a no-op.                                                  */
+int dh_math_probe(dh_ctx* ctx, int fn, const double* x, const double* y, int64_t n, double* out0,
+                  double* out1);
 /* Page-locked host memory from a process-wide cache (hipHostMalloc; a freed block serves the next
  * request of up to 1.25x its size): the generator's output arrays.  dh_host_cache_trim releases
  * the cached blocks.                                                                             */

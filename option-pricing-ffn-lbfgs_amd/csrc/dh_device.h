@@ -29,8 +29,11 @@ __device__ __forceinline__ cplx cmul(cplx a, cplx b) {
 }
 __device__ __forceinline__ cplx cscale(cplx a, double s) { return {a.re * s, a.im * s}; }
 
-// Smith's algorithm with a reciprocal scale factor (NumPy scalar complex division).
+// Smith's algorithm with a reciprocal scale factor (NumPy scalar complex division): NumPy's bits,
+// zero divisor included (no contraction: a fused b.re + b.im * rat is not NumPy's sum), and within
+// 2 ulp of |z| per component (tests/test_gpu_math.py, against the exact quotient).
 __device__ __forceinline__ cplx cdiv(cplx a, cplx b) {
+#pragma clang fp contract(off)
     const double abr = fabs(b.re), abi = fabs(b.im);
     if (abr >= abi) {
         if (abr == 0.0 && abi == 0.0) return {a.re / abr, a.im / abr};
@@ -44,6 +47,7 @@ __device__ __forceinline__ cplx cdiv(cplx a, cplx b) {
 }
 
 // Principal square root (Re >= 0), glibc csqrt identity 2 Re Im = Im z for the small half.
+// Signs and zeros as NumPy's complex sqrt; each component within 2 ulp of |sqrt z|.
 __device__ __forceinline__ cplx csqrt_p(cplx z) {
     const double x = z.re, y = z.im;
     if (x == 0.0 && y == 0.0) return {0.0, y};
@@ -58,8 +62,9 @@ __device__ __forceinline__ cplx csqrt_p(cplx z) {
 
 // sin and cos of one argument: 3-part Cody-Waite reduction by pi/2 with FMA, then the fdlibm
 // kernel polynomials on [-pi/4, pi/4] (coefficients of __kernel_sin / __kernel_cos).  Max error
-// ~2 ulp for |x| < 2^20 (every argument on this path is bounded by N pi plus the CF phases);
-// accuracy degrades gracefully beyond, and non-finite x gives NaN like libm.  Replaces ocml's
+// 2 ulp of the result for |x| < 2^20 (every argument on this path is bounded by N pi plus the CF
+// phases; measured 1.2, profiles/math_accuracy.json); beyond, for 2^20 <= |x| < 2^31, no accuracy
+// bound but finite results within the unit circle; non-finite x gives NaN like libm.  Replaces ocml's
 // sincos, whose inlined Payne-Hanek branch costs ~100 VGPRs per call site.
 __device__ __forceinline__ double flip_sign(double v, int neg) {   // neg: 0 or 1
     return __hiloint2double(__double2hiint(v) ^ (neg << 31), __double2loint(v));
@@ -116,7 +121,15 @@ __device__ __forceinline__ void dsincos(double x, double* sp, double* cp) {
 // 3-part FMA Cody-Waite reduction of dsincos scaled by 2^-5, exact), sin/cos(q pi/64) from an LDS
 // copy of kSinCosPi64 (one ds_read_b128; correctly rounded entries), sin r and cos r by Taylor
 // polynomials through r^7 / r^8 (the next terms are < 1e-18 relative), then the angle-addition
-// formulas.  ~1 ulp for |x| < 2^20; 17 VALU instructions against dsincos's 41.
+// formulas.  Absolute, not relative, accuracy: within 2 units of 2^-53 for |x| < 2^20 (measured
+// 1.8; half a unit each from the two table entries and the final rounding, the rest the product's
+// rounding and the reduction), which is within 2 ulp of the result only where |result| >= 2^-5;
+// near a zero of sin or cos the error relative to the result grows as 1 / |result|.  The one
+// exception is at the zeros themselves: where the table entry is exactly 0 (sin at multiples of
+// pi, cos at odd multiples of pi/2) the result is -+sin r alone, and the 3-part reduction keeps r,
+// and so the result however small, within 2 ulp of itself (asserted at the doubles closest to
+// k pi/2).  Beyond, for
+// 2^20 <= |x| < 2^31, and for non-finite x: as dsincos.  17 VALU instructions against dsincos's 41.
 // Table lookups of the CF loop round their index with the 1.5 * 2^52 shift: qd = fma(x, c, shift)
 // is shift + rint(x c) (its ulp is 1) and the low word of qd holds rint(x c) as a two's-
 // complement integer, so the index needs no float-to-int conversion (a NaN x gives a defined
@@ -143,8 +156,9 @@ __device__ __forceinline__ void dsincos_t(double x, const double2* __restrict__ 
 }
 
 // exp(x): restates the ROCm device library's __ocml_exp_f64 operation for operation (same
-// reduction constants, degree-11 polynomial and range clamps, so the same bits), with the
-// polynomial steps in the fma_k form.
+// reduction constants, degree-11 polynomial and range clamps), with the polynomial steps in the
+// fma_k form.  2 ulp (measured 1.0, subnormal results included, which ldexp
+// rounds once); inf for x > 709.79, 0 for x < -745.2, NaN for NaN.
 __device__ __forceinline__ double dexp(double x) {
     const double q = rint(x * 0x1.71547652b82fep+0);                 // x log2(e)
     double r = fma(q, -0x1.62e42fefa39efp-1, x);                      // x - q ln2 (2 parts)
@@ -165,7 +179,7 @@ __device__ __forceinline__ double dexp(double x) {
     return (x < -1075.0) ? 0.0 : e;
 }
 
-// dexp for x <= 0 (or -inf / NaN): the same bits without the overflow select (the CF's
+// dexp for x <= 0 (or -inf / NaN): dexp's bits without the overflow select (the CF's
 // e^{-Re(d) tau} and Gaussian jump factor e^{-sj^2 u^2 / 2}).
 __device__ __forceinline__ double dexp_nonpos(double x) {
     const double q = rint(x * 0x1.71547652b82fep+0);
@@ -199,9 +213,17 @@ __device__ __forceinline__ cplx clog_(cplx z) { return {log(hypot(z.re, z.im)), 
 // Measured on gfx950 (tools/ubench/fp64_latency.hip, cycles of issue per wave64): IEEE division
 // ~70, ocml sqrt ~110, exp ~120, ocml log ~456, ocml atan2 ~255, an fp64 FMA ~5.5.  The COS
 // table is issue-bound, so these restate the needed functions with v_rcp_f64 / v_rsq_f64 seeds
-// and Newton/Goldschmidt steps (<= ~2 ulp; NaN in gives NaN out; used on finite operands).
+// and Newton/Goldschmidt steps (each function's comment has its bound, asserted against mpmath
+// truth by tests/test_gpu_math.py; NaN in gives NaN out; used on finite operands).
 
-// 1/x: v_rcp_f64 seed + two Newton steps.
+// 1/x: v_rcp_f64 seed + two Newton steps; 2 ulp (measured 0.5, and the same in units of 2^-1074
+// where 1/x is subnormal, |x| > 2^1022).  Domain: 2^-1023 <= |x| < inf, subnormals from 2^-1023 up
+// included.  Below 2^-1024 the reciprocal overflows and the result is NaN, not inf (the seed is inf,
+// and inf - inf follows), as it is for 0 and inf; between 2^-1024 and 2^-1023 an overflowing seed
+// can do the same, so that binade is outside the domain too.  No
+// caller reaches these: dlog's 2 + f is in [2.7, 3.5), datan2 clamps its denominator to the smallest
+// normal, datan2_t's is >= max(|x|, |y|) of a nonzero D conj(d), cdiv_rcp's |z2|^2 is within
+// 2^+-200, and the COS terms pass 1 + u^2 and u = k pi / (b - a), k >= 1.
 __device__ __forceinline__ double drcp(double x) {
     double r = __builtin_amdgcn_rcp(x);
     double e = fma(-x, r, 1.0);
@@ -210,7 +232,15 @@ __device__ __forceinline__ double drcp(double x) {
     return fma(r, e, r);
 }
 
-// sqrt(x) and 1/sqrt(x) together: v_rsq_f64 seed + one Goldschmidt step + residual correction.
+// sqrt(x) and 1/sqrt(x) together: v_rsq_f64 seed + one Goldschmidt step + residual correction,
+// for normal x > 0.  sq is within 2 ulp (measured 0.6: the residual step removes the seed's error).
+// rs is NOT: it is 2 h after the one Goldschmidt step, with no correction of its own.  Budget: a
+// seed y0 = (1 + e0) / sqrt(x) gives r = -e0 - e0^2 / 2 and h (1 + r) = (1 - 1.5 e0^2) / (2 sqrt(x)),
+// so rs carries 1.5 e0^2 relative, plus one ulp for the roundings of g (through r) and of the last
+// FMA.  AMD's ISA manuals give v_rsq_f64 a precision of 2^29 ulp, e0 <= 2^-23: 1.5 * 2^-46, which
+// is up to 192 ulp of rs, 193 with the roundings (kRsqrtUlpBudget in tests/test_gpu_math.py).
+// Measured 17.6 ulp (e0 ~ 2^-24.7).  Its users take it where ~2e-15 relative is enough: 1 / |dd|
+// inside log |Q|^2, and the smaller component of sqrt(dd).
 __device__ __forceinline__ void dsqrt_rsqrt(double x, double& sq, double& rs) {
     const double y0 = __builtin_amdgcn_rsq(x);
     double g = x * y0, h = 0.5 * y0;
@@ -242,7 +272,8 @@ __device__ __forceinline__ void dsqrt_rsqrt_pos(double x, double& sq, double& rs
     rs = 2.0 * h;
 }
 
-// log(x): fdlibm e_log.c, x = 2^k (1 + f), sqrt(1/2) <= 1 + f < sqrt(2), s = f / (2 + f).
+// log(x): fdlibm e_log.c, x = 2^k (1 + f), sqrt(1/2) <= 1 + f < sqrt(2), s = f / (2 + f).  2 ulp of
+// the result (measured 0.7), subnormal x included; libm's special values.
 __device__ __forceinline__ double dlog(double x) {
     int k;
     double m = frexp(x, &k);                         // m in [0.5, 1)
@@ -275,7 +306,14 @@ __device__ __forceinline__ double dlog(double x) {
 // Branch-free (every case is a select the compiler keeps as one): zeros need no special case
 // (the reciprocal's argument is clamped to the smallest normal, so t = 0 for x = y = 0, and the
 // sign bit of x selects pi - a, giving atan2(+-0, -0) = +-pi); the one deviation from libm is
-// x = -0 with y != 0, which returns pi/2 one ulp high.
+// x = -0 with y != 0, which returns pi/2 one ulp high.  Finite operands: an infinite one gives NaN
+// (libm: a multiple of pi/4), as does any NaN.
+// Accuracy: 2 ulp of the result except just above the pi/8 switch, where the result (~pi/8, ulp
+// 2^-54) is formed as pi/4 + at with |at| up to pi/8.  Budget there, in u = 2^-53 relative to at:
+// mn - mx and mn + mx one each, the reciprocal one (0.5 ulp measured), the product one, the
+// polynomial one (fdlibm's own bound), at = tr - tr (s1 + s2) one: 6 u |at| <= 2.36 * 2^-53 = 4.7
+// ulp of the result; at + lo 0.5, the final sum 0.5: 5.7, asserted as 6 ulp.  Measured 2.1 (at
+// t = tan(pi/8) + 1 ulp).  No production kernel calls this form (the CF uses datan2_t).
 __device__ __forceinline__ double datan2(double y, double x) {
     const double ax = fabs(x), ay = fabs(y);
     const double mx = fmax(ax, ay), mn = fmin(ax, ay);
@@ -313,8 +351,9 @@ constexpr int kMathTab = 353;
 // log(x) for normal x > 0 (glibc's table layout, tools/gen_logatan_tables.py): x = 2^k z with z
 // in [0.6875, 1.375) from the bits, subinterval i by the next 7 bits, r = z invc_i - 1 (one FMA,
 // |r| < 2^-8), log x = k ln2 + logc_i + log1p(r) with log1p by its Taylor series through r^7
-// (remainder < 2^-67).  Absolute error ~1 ulp of the result's scale (no special path near 1,
-// where only absolute accuracy matters here).  ~20 VALU against dlog's ~40.
+// (remainder < 2^-67).  Absolute error within 2 ulp of max(|log x|, 2^-8) (measured 1.0; no
+// special path near 1, where only absolute accuracy matters here, so the error relative to the
+// result is unbounded as x -> 1).  ~20 VALU against dlog's ~40.
 __device__ __forceinline__ double dlog_t(double x, const double2* __restrict__ tab) {
     // glibc's 64-bit integer steps on the high word only (the constant's low word is 0, so the
     // subtraction never borrows): tmp = hi(x) - 0x3fe60000, i = tmp >> 13 & 127, k = tmp >> 20
@@ -343,8 +382,14 @@ __device__ __forceinline__ double dlog_t(double x, const double2* __restrict__ t
 // table: t = min/max(|x|, |y|) in [0, 1] (the v_rcp_f64 seed is enough to pick j = rint(64 t)),
 // then atan t = atan(j/64) + atan(t') with t' = (mn - mx s)/(mx + mn s), s = j/64 exact, both
 // FMAs; atan t' to t'^7.  Same quadrant rules as datan2.  For the CF only: x, y finite and not
-// both 0 (D conj(d)), no NaN handling -- a NaN D makes log|Q|^2 NaN (dlog_t), and so the price.
-// ~35 VALU against datan2's ~50.
+// both 0 (D conj(d)), no NaN handling -- a NaN D makes log|Q|^2 NaN (dlog_t), and so the price;
+// (0, 0) gives NaN.  2 ulp of the result (measured 1.3).  ~35 VALU against datan2's ~50.
+// Where no quadrant step follows (x > 0, |y| <= x) and j >= 16 the result is hi + (at + lo) and the
+// budget is tighter.  In u = 2^-53: t' carries 7 u (yp and xp one each, the reciprocal 4 = drcp's 2
+// ulp, the product one), at one more for its last FMA (the series' remainder t'^8 / 9 < 2^-59), so
+// |at| <= 2^-7 is off by <= 8 u 2^-7 = 2^-57; at + lo rounds by <= 2^-60; together 1.125 * 2^-57,
+// which is <= 9/32 ulp of a result >= atan(1/4) - 2^-7 > 2^-3; the final sum adds 1/2: 25/32 ulp.
+// Without the table's lo (up to 1/2 ulp of hi) this does not hold.
 __device__ __forceinline__ double datan2_t(double y, double x, const double2* __restrict__ tab) {
     const double ax = fabs(x), ay = fabs(y);
     const double mx = fmax(ax, ay), mn = fmin(ax, ay);
@@ -371,9 +416,12 @@ __device__ __forceinline__ double datan2_t(double y, double x, const double2* __
 // ln2/128, q = 64 e + j rounded by the 1.5 * 2^52 shift (its low word IS q, so no float-to-int
 // conversion: a NaN x indexes a defined entry and stays NaN through r), e^r - 1 by its Taylor
 // series through r^5 (remainder < 4e-17 relative), then 2^e (t + t (e^r - 1)) with t = 2^(j/64)
-// correctly rounded.  ~1 ulp (a hi + lo table would give ~0.5 ulp but held two more VGPRs live
+// correctly rounded.  2 ulp (measured 1.13: half an ulp each from the table entry and the last
+// FMA, the rest the polynomial's; a hi + lo table would give ~0.5 ulp but held two more VGPRs live
 // across the polynomial: spills in the <= 96-VGPR fused build); 11 fp64 VALU against dexp's 19.
-// Finite x <= 709 (the CF's exponents); callers select the overflow / underflow ends.
+// Subnormal results are rounded once, by ldexp.  Finite x <= 709.78 (the CF's exponents); callers
+// select the overflow / underflow ends: dexp_t is inf where e^x overflows or x > 709.8, and both
+// forms are 0 for x < -745.2.
 __device__ __forceinline__ double dexp_t_core(double x, const double2* __restrict__ tab) {
     const double qd = fma(x, 0x1.71547652b82fep+6, kShift52);        // rint(x 64/ln2)
     const double q = qd - kShift52;
@@ -400,7 +448,10 @@ __device__ __forceinline__ double dexp_t_nonpos(double x, const double2* __restr
 }
 
 // z1 / z2 through one reciprocal of |z2|^2 (no Smith scaling: |z2| on this path stays far
-// from the fp64 over/underflow thresholds).
+// from the fp64 over/underflow thresholds; tested on 2^-100 <= |z2| <= 2^100).  Error per
+// component, in u = 2^-53 of |z|: |z2|^2 two (a product and the FMA), its reciprocal one, each
+// numerator sum two (|p1| + |p2| <= |z1| |z2|, and the sum's own rounding), the final product one:
+// 6 u |z| <= 6 ulp of |z| (measured 2.2).
 __device__ __forceinline__ cplx cdiv_rcp(cplx a, cplx b) {
     const double inv = drcp(fma(b.re, b.re, b.im * b.im));
     return {(a.re * b.re + a.im * b.im) * inv, (a.im * b.re - a.re * b.im) * inv};

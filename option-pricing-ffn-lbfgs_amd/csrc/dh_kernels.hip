@@ -5161,3 +5161,4 @@ extern "C" int dh_allgather_best(dh_comm* c, const double* rec, int rows, int wi
 
 #include "dh_gen_device.h"
 #include "dh_iv.h"
+#include "dh_math_probe.h"

@@ -104,6 +104,7 @@ SIGNATURES = {
                                 C.c_double, C.c_double, C.c_int, C.c_double, _dp, C.c_int64,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp]),
     "dh_gen_log": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    "dh_math_probe": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, _vp, _vp]),
     "dh_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_vp)]),
     "dh_host_free": (C.c_int, [_vp]),
     "dh_host_cache_trim": (C.c_int, []),
@@ -1069,6 +1070,46 @@ def gen_log(x, ctx=None) -> np.ndarray:
     return out
 
 
+# dh_math_probe's function ids (include/dhcos.h)
+MATH_PROBE_FNS = {name: i for i, name in enumerate((
+    "dsincos", "dsincos_t", "dexp", "dexp_nonpos", "dexp_t", "dexp_t_nonpos", "dlog", "dlog_t",
+    "datan2", "datan2_t", "drcp", "dsqrt_rsqrt", "dsqrt_rsqrt_pos", "csqrt_p", "cdiv",
+    "cdiv_rcp"))}
+_PROBE_TWO_ARGS = ("datan2", "datan2_t", "csqrt_p", "cdiv", "cdiv_rcp")
+_PROBE_TWO_OUT = ("dsincos", "dsincos_t", "dsqrt_rsqrt", "dsqrt_rsqrt_pos", "csqrt_p", "cdiv",
+                  "cdiv_rcp")
+
+
+def math_probe(fn_name, x, y=None, ctx=None):
+    """dh_math_probe: one fp64 elementary function of csrc/dh_device.h over arrays (test support).
+    x: the argument, atan2's first argument or the real part; y: atan2's second argument or the
+    imaginary part.  cdiv / cdiv_rcp take x = [a.re | b.re], y = [a.im | b.im] (two halves of n
+    each) and return n quotients.  -> out0, or (out0, out1) for sincos (sin, cos), sqrt_rsqrt
+    (sqrt, rsqrt) and the complex helpers (re, im)."""
+    if not isinstance(fn_name, str):
+        raise TypeError("math_probe: the function is given by name (MATH_PROBE_FNS)")
+    fn = MATH_PROBE_FNS.get(fn_name, -1)          # an unknown name: DH_E_ARG from the library
+    x = _f64(x).ravel()
+    two = fn_name in _PROBE_TWO_ARGS
+    if two:
+        if y is None:
+            raise ValueError(f"math_probe: {fn_name} takes two arrays")
+        y = _f64(y).ravel()
+        if y.size != x.size:
+            raise ValueError("math_probe: x and y differ in size")
+    n = x.size
+    if fn_name in ("cdiv", "cdiv_rcp"):
+        if n % 2:
+            raise ValueError("math_probe: cdiv takes two operands (x and y of 2 n entries)")
+        n //= 2
+    out0, out1 = np.empty(n), np.empty(n)
+    ctx = ctx or default_context()
+    _check(load().dh_math_probe(ctx.handle, fn, x.ctypes.data if n else None,
+                                y.ctypes.data if two and n else None, n,
+                                out0.ctypes.data if n else None, out1.ctypes.data if n else None))
+    return (out0, out1) if fn_name in _PROBE_TWO_OUT else out0
+
+
 def gen_device(surf, n_samples, lo, hi, alpha, spot0, ret_mu, ret_sigma, noise_sigma, r, k_rel,
                N=128, L=10.0, first_day=None, stats=None):
     """dh_gen_device on NumPy's global legacy RandomState: the generator's samples drawn, blended,
@@ -1121,4 +1162,5 @@ __all__ = ["gen_draw", "gen_assemble", "gen_dates", "gen_locate", "gen_draw_loca
            "LIB_PATH",
            "SIGNATURES",
            "Comm", "comm_id", "best_start", "COMM_ID_BYTES", "FgChannel", "pinned",
-           "pinned_empty", "host_cache_trim", "gen_device", "gen_log"]
+           "pinned_empty", "host_cache_trim", "gen_device", "gen_log",
+           "math_probe", "MATH_PROBE_FNS"]

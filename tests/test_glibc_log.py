@@ -16,8 +16,10 @@ LIB = os.path.join(ROOT, "tests", "native", "liblogcheck.so")
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(LIB):
-        pytest.skip("tests/native/liblogcheck.so not built (make -C option-pricing-ffn-lbfgs_amd/csrc)")
+    if not os.path.exists(LIB):               # host code only (g++): built on demand, never skipped
+        import subprocess
+        subprocess.run(["make", "-C", os.path.join(ROOT, "option-pricing-ffn-lbfgs_amd", "csrc"),
+                        "logcheck"], check=True, capture_output=True)
     L = ctypes.CDLL(LIB)
     L.dh_log_mismatches.restype = ctypes.c_int64
     L.dh_log_mismatches.argtypes = [ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(ctypes.c_double)]

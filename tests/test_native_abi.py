@@ -22,7 +22,7 @@ def header_functions():
 def test_header_declares_expected_entry_points():
     fns = header_functions()
     for f in ("dh_surface_price", "dh_surface_loss", "dh_price_pairs", "dh_cf", "dh_trunc_range",
-              "dh_cos_coeffs", "dh_surface_loss_dev", "dh_surface_price_dev"):
+              "dh_cos_coeffs", "dh_surface_loss_dev", "dh_surface_price_dev", "dh_math_probe"):
         assert f in fns
 
 
@@ -90,6 +90,20 @@ def test_null_and_range_arguments_are_rejected():
     assert np.int8(1) == 1
     for setter in (lib.dh_ctx_set_tail_cut, lib.dh_ctx_set_exact, lib.dh_ctx_set_path):
         assert setter(None, 1) == -1                  # a null context, not a crash
+
+
+def test_math_probe_arguments_are_rejected():
+    """dh_math_probe (test support) validates its context before any device work, and the binding's
+    name table is the header's list of function ids, in order."""
+    from dhcos import _native
+    lib = _native.load()
+    assert lib.dh_math_probe(None, 0, None, None, 0, None, None) == -1
+    assert b"null" in lib.dh_last_error()
+    txt = open(HEADER).read()
+    doc = txt[txt.index("fn: 0 dsincos"):txt.index("any other value gives DH_E_ARG")]
+    ids = {name: int(i) for i, name in re.findall(r"(\d+) ([a-z_0-9]+)", doc)}
+    assert ids == _native.MATH_PROBE_FNS and len(ids) == 16
+    assert "math_probe" in _native.__all__
 
 
 def test_gen_assemble_arguments_are_rejected():

@@ -1,6 +1,9 @@
 // Accuracy of the CF loop's table-driven primitives against the device library (ocml, ~0.5-1
 // ulp): dexp_t over [-708, 709] (normal results), dsincos_t over [-2^12, 2^12], dlog_t over (1e-300, 1e300),
 // datan2_t over random quadrants.  Prints the max error in units of the reference's last place.
+// Superseded by tests/test_gpu_math.py and tools/math_accuracy.py, which compare every primitive
+// with mpmath truth at structured edge points (profiles/math_accuracy.json); kept as a quick
+// random-point cross-check against ocml.
 //   hipcc -O3 --offload-arch=gfx950 -I../../option-pricing-ffn-lbfgs_amd/csrc math_accuracy.hip
 #include <hip/hip_runtime.h>
 #include <cmath>
