@@ -376,6 +376,45 @@ int dh_implied_vol_dev(dh_ctx* ctx, const double* d_price, const double* d_S0, c
 int dh_surface_implied_vol(dh_ctx* ctx, const dh_surface* s, const double* params, int64_t P,
                            int N, double L, double* iv, double* prices);
 
+/* ---- calibration objective in implied-vol space (csrc/dh_iv_loss.h) --------- */
+/* Replaces nothing in the reference (its only objective is the relative price error of
+ * dh_surface_loss); it replaces pulling dh_surface_implied_vol's [S][M] vols to the host and
+ * summing them there on every request of a vol-space fit.
+ * Market vols of the surface: mkt_iv[M] and weight[M] (host arrays, the caller's option order;
+ * weight NULL = every weight 1), copied to the device; a second call replaces the first's data.
+ * DH_E_ARG if a weight is negative or not finite, if the weights sum to zero, or if mkt_iv[m] is
+ * negative or not finite where weight[m] > 0 (where the weight is 0 it may hold anything).      */
+int dh_surface_set_iv_market(dh_surface* s, const double* mkt_iv, const double* weight);
+/* The reduction stage alone, over prices already on the device: d_prices [S][M] as
+ * dh_surface_price_dev writes them (the caller's option order), d_params the records they were
+ * priced under.  Per param set s and option m, with S0, r, q from the record, K, T, is_call of the
+ * option (DH_STRIKE_PCT_SPOT: the strike dh_surface_implied_vol forms):
+ *   bad      price NaN, +-inf or <= 0 (dh_surface_loss's rule), or a vol that does not exist
+ *            (price >= upper, T <= 0, legs out of range: dh_implied_vol's NaN)
+ *   v        dh_implied_vol's sigma of the price (the same device function, the same bits); 0.0
+ *            where price < lower -- the vol's continuous extension, so that a deep in-the-money
+ *            model price a rounding below intrinsic does not turn the loss into 1e10
+ *   iv[s*M + m] = v as used: 0.0 where clamped, NaN where bad; every option, whatever its weight
+ *                 (d_iv NULL to skip)
+ *   sse[s]   = sum of weight[m] (v - mkt_iv[m])^2 over options with weight[m] > 0 that are not bad
+ *   n_bad[s] = #{m : weight[m] > 0 and option m is bad}
+ * The host forms loss = n_bad ? 1e10 : sse / sum(weight) + feller.  sse[s] is summed in an order
+ * fixed by the surface alone and depends on nothing but record s: the same bits in any request,
+ * at any place in it, on any stream.  Enqueues on `stream` (NULL = the context's); no
+ * synchronisation, no allocation after warm-up.  DH_E_ARG on a surface without market vols.    */
+int dh_surface_iv_sse_dev(dh_ctx* ctx, const dh_surface* s, const double* d_params,
+                          const double* d_prices, int S, double* d_sse, int32_t* d_n_bad,
+                          double* d_iv, void* stream);
+/* Price, then reduce, on one stream: dh_surface_price_dev into d_prices (NULL: context scratch),
+ * then the stage above (d_iv NULL to skip the vols).                                            */
+int dh_surface_loss_iv_dev(dh_ctx* ctx, const dh_surface* s, const double* d_params, int S, int N,
+                           double L, double* d_sse, int32_t* d_n_bad, double* d_prices,
+                           double* d_iv, void* stream);
+/* The host-pointer form, synchronous as dh_surface_loss: params [S][16] in, sse [S], n_bad [S] and
+ * the optional prices [S][M], iv [S][M] out (NULL to skip either).                              */
+int dh_surface_loss_iv(dh_ctx* ctx, const dh_surface* s, const double* params, int S, int N,
+                       double L, double* sse, int32_t* n_bad, double* prices, double* iv);
+
 /* ---- building blocks (exposed for API parity with the reference's public methods) -------- */
 /* phi(u_j; tau) for one param set: DoubleHeston.characteristic_function (double_heston.py:48-97) */
 int dh_cf(dh_ctx* ctx, const double* params, const double* u, int n, double tau, double* re,

@@ -2887,6 +2887,7 @@ struct dh_ctx {
     std::vector<std::pair<std::array<int64_t, 3>, int>> resident_fused;
     GenBufs* gen = nullptr;    // the generator's device draw (dh_gen_device)
     DevBuf iv;                 // quote columns / vols of dh_implied_vol, dh_surface_implied_vol
+    DevBuf iv_part_sse, iv_part_bad;   // tile partials of dh_surface_iv_sse_dev (dh_iv_loss.h)
 };
 
 struct dh_surface {
@@ -2908,6 +2909,12 @@ struct dh_surface {
     double* group_T = nullptr;
     int2* groups = nullptr;
     void* block = nullptr;  // the one device allocation every array above points into
+    // dh_surface_set_iv_market (dh_iv_loss.h): market vols and weights [M] in the caller's option
+    // order, in an allocation of their own
+    bool has_iv = false;
+    double* iv_mkt = nullptr;
+    double* iv_wgt = nullptr;
+    void* iv_block = nullptr;
     std::vector<double> h_group_T;   // host copies of group_T / groups (the fused launch's
     std::vector<int2> h_groups;      // kernel arguments, KargParams)
 };
@@ -3433,7 +3440,8 @@ int dh_ctx_destroy(dh_ctx* ctx) {
                       &ctx->consts, &ctx->cl_mask, &ctx->cl_price, &ctx->aux0,
                       &ctx->aux1, &ctx->aux2, &ctx->aux3, &ctx->pre, &ctx->lb_state, &ctx->lb_rec,
                       &ctx->lb_sse, &ctx->lb_bad, &ctx->lb_live, &ctx->lb_done, &ctx->lb_x0,
-                      &ctx->lb_trace, &ctx->lb_trace_n, &ctx->iv})
+                      &ctx->lb_trace, &ctx->lb_trace_n, &ctx->iv, &ctx->iv_part_sse,
+                      &ctx->iv_part_bad})
         b->release();
     ctx->h_params.release();
     ctx->h_loss.release();
@@ -3604,6 +3612,7 @@ int dh_surface_destroy(dh_surface* s) {
     if (!s) return DH_OK;
     DeviceScope dev_scope(s->ctx ? s->ctx->device : 0);
     if (s->block) (void)hipFree(s->block);
+    if (s->iv_block) (void)hipFree(s->iv_block);
     delete s;
     return DH_OK;
 }
@@ -5161,4 +5170,5 @@ extern "C" int dh_allgather_best(dh_comm* c, const double* rec, int rows, int wi
 
 #include "dh_gen_device.h"
 #include "dh_iv.h"
+#include "dh_iv_loss.h"
 #include "dh_math_probe.h"

@@ -123,6 +123,12 @@ SIGNATURES = {
     "dh_implied_vol_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
     "dh_surface_implied_vol": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_double, _vp,
                                          _vp]),
+    "dh_surface_set_iv_market": (C.c_int, [_vp, _vp, _vp]),
+    "dh_surface_iv_sse_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "dh_surface_loss_iv_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp,
+                                         _vp, _vp, _vp]),
+    "dh_surface_loss_iv": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp,
+                                     _vp]),
     "dh_cf": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, _dp, _dp]),
     "dh_cf_complex": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp]),
     "dh_trunc_range": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int64, C.c_double, _dp, _dp]),
@@ -602,6 +608,34 @@ class Surface:
                                                  None if prices is None else prices.ctypes.data))
         return (iv, prices) if want_prices else iv
 
+    def set_iv_market(self, mkt_iv, weight=None):
+        """dh_surface_set_iv_market: the market vols [M] (and weights [M], default all 1) of the
+        vol-space objective, in the surface's option order; a second call replaces the first."""
+        iv = _f64(mkt_iv).reshape(-1)
+        w = None if weight is None else _f64(weight).reshape(-1)
+        if iv.size != self.M or (w is not None and w.size != self.M):
+            raise ValueError(f"mkt_iv and weight must hold {self.M} values")
+        with self.ctx._lock:
+            _check(load().dh_surface_set_iv_market(self._h, iv.ctypes.data,
+                                                   None if w is None else w.ctypes.data))
+
+    def loss_terms_iv(self, params, N=128, L=10.0, want_prices=False, want_iv=False):
+        """dh_surface_loss_iv -> (sse[S], n_bad[S][, prices[S,M]][, iv[S,M]]): the weighted
+        squared vol errors against set_iv_market's vols and the count of weighted options without
+        a vol; iv holds the vols as used (0.0 where clamped at the lower bound, NaN where bad)."""
+        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        S = params.shape[0]
+        sse = np.empty(S)
+        bad = np.empty(S, dtype=np.int32)
+        prices = np.empty((S, self.M)) if want_prices else None
+        iv = np.empty((S, self.M)) if want_iv else None
+        with self.ctx._lock:
+            _check(load().dh_surface_loss_iv(self.ctx.handle, self._h, params.ctypes.data, S,
+                                             int(N), float(L), sse.ctypes.data, bad.ctypes.data,
+                                             None if prices is None else prices.ctypes.data,
+                                             None if iv is None else iv.ctypes.data))
+        return (sse, bad) + ((prices,) if want_prices else ()) + ((iv,) if want_iv else ())
+
     # device-pointer variants (torch tensors or raw device addresses)
     def price_dev(self, d_params: int, P: int, d_out: int, N=128, L=10.0, stream: int = 0):
         _check(load().dh_surface_price_dev(self.ctx.handle, self._h, _vp(d_params), int(P), int(N),
@@ -613,6 +647,23 @@ class Surface:
                                           float(L), _vp(d_sse), _vp(d_bad),
                                           _vp(d_prices) if d_prices else None,
                                           _vp(stream) if stream else None))
+
+    def iv_sse_dev(self, d_params: int, d_prices: int, S: int, d_sse: int, d_bad: int,
+                   d_iv: int = 0, stream: int = 0):
+        """dh_surface_iv_sse_dev: the vol-space reduction over [S, M] prices on the device."""
+        _check(load().dh_surface_iv_sse_dev(self.ctx.handle, self._h, _vp(d_params),
+                                            _vp(d_prices), int(S), _vp(d_sse), _vp(d_bad),
+                                            _vp(d_iv) if d_iv else None,
+                                            _vp(stream) if stream else None))
+
+    def loss_iv_dev(self, d_params: int, S: int, d_sse: int, d_bad: int, d_prices: int = 0,
+                    d_iv: int = 0, N=128, L=10.0, stream: int = 0):
+        """dh_surface_loss_iv_dev: price, then reduce in vol space, on one stream."""
+        _check(load().dh_surface_loss_iv_dev(self.ctx.handle, self._h, _vp(d_params), int(S),
+                                             int(N), float(L), _vp(d_sse), _vp(d_bad),
+                                             _vp(d_prices) if d_prices else None,
+                                             _vp(d_iv) if d_iv else None,
+                                             _vp(stream) if stream else None))
 
 
 class FgChannel:

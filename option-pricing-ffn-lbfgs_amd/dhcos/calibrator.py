@@ -14,6 +14,10 @@ What changes relative to the reference, and what does not:
     start's 14 points share one launch (S = 14 x starts param sets).
   * Starts are independent, so the per-start trajectory does not depend on how many starts share
     a launch; the best start is chosen with the reference's strict ``<`` in start order.
+  * ``objective="iv"`` (not in the reference) fits in implied-vol space: the loss is the weighted
+    mean squared difference of model and market Black-Scholes vols plus the Feller penalty, the
+    vols inverted and summed on the device (csrc/dh_iv_loss.h).  The default
+    ``objective="price"`` is the reference's loss on the code paths it always took.
   * SciPy's optimizer itself is driven through its reverse-communication entry point
     (``scipy.optimize._lbfgsb.setulb``) by ``lbfgsb_steps``, a line-for-line restatement of
     ``_minimize_lbfgsb``'s loop for jac=True and no bounds: one Python thread advances every
@@ -36,7 +40,7 @@ from scipy.optimize._lbfgsb_py import status_messages, task_messages
 from threadpoolctl import ThreadpoolController
 
 from . import _native
-from .pricer import resolve_call
+from .pricer import implied_vol, resolve_call
 
 INVALID_LOSS = 1e10                 # lbfgs_calibrator.py:152-158,176-177
 FD_ABS_STEP = 1e-8                  # SciPy L-BFGS-B default eps (scipy/_lbfgsb_py.py:290)
@@ -210,8 +214,32 @@ def fd_request_points_many(X0, h=FD_ABS_STEP):
 class DoubleHestonJumpCalibrator:
     """Calibrates the 13 Double-Heston + jump parameters to a list of market options."""
 
+    objective = "price"        # a subclass that skips __init__ keeps the reference's objective
+
     def __init__(self, spot: float, risk_free_rate: float, market_options: List[Dict], *,
-                 N: int = 128, device=None):
+                 N: int = 128, device=None, objective: str = "price", market_ivs=None,
+                 iv_weights=None):
+        """objective="price": the reference's relative price error.  objective="iv": the weighted
+        mean squared error of the Black-Scholes vols, sum_m w_m (iv_model - iv_mkt)^2 / sum(w), with
+        market_ivs the market's vols (default: the device inversion of the option prices at spot,
+        rate and q = 0, formed with the surface) and iv_weights the w_m (default 1; 0 drops an
+        option).  A market vol that is not finite at a non-zero weight raises ValueError."""
+        if objective not in ("price", "iv"):
+            raise ValueError(f"objective must be 'price' or 'iv', not {objective!r}")
+        self.objective = objective
+        self.market_ivs = self.iv_weights = None
+        if objective == "iv":
+            M = len(market_options)
+            if market_ivs is not None:
+                self.market_ivs = np.array(market_ivs, dtype=np.float64).reshape(M)
+            w = np.ones(M) if iv_weights is None else np.array(iv_weights,
+                                                               dtype=np.float64).reshape(M)
+            if not np.all(np.isfinite(w) & (w >= 0)):
+                raise ValueError("iv_weights must be finite and non-negative")
+            if M and not w.sum() > 0:
+                raise ValueError("iv_weights sum to zero")
+            self.iv_weights = w
+            self._iv_wsum = float(w.sum())
         self.spot = spot
         self.risk_free_rate = risk_free_rate
         self.market_options = market_options
@@ -262,9 +290,32 @@ class DoubleHestonJumpCalibrator:
                 return None
             ctx = _native.default_context(self.device)
             K, T = self._option_arrays()
-            self._surface = _native.Surface(ctx, K, T, flags, self.market_prices)
+            surf = _native.Surface(ctx, K, T, flags, self.market_prices)
+            if self.objective == "iv":
+                try:
+                    self._set_iv_market(surf, K, T, flags)
+                except BaseException:
+                    surf.close()
+                    raise
+            self._surface = surf
             self._surface_ok = True
         return self._surface if self._surface_ok else None
+
+    def _set_iv_market(self, surf, K, T, flags):
+        """objective="iv": the market vols (given, or the option prices inverted on the device
+        with spot, rate and q = 0) and the weights onto the surface."""
+        iv = self.market_ivs
+        if iv is None:
+            iv = implied_vol(self.market_prices, self.spot, K, T, self.risk_free_rate, 0.0,
+                             np.asarray(flags, dtype=bool), device=self.device)
+            iv = np.asarray(iv, dtype=np.float64).reshape(len(flags))
+        wrong = np.flatnonzero((self.iv_weights > 0) & ~(np.isfinite(iv) & (iv >= 0)))
+        if wrong.size:
+            raise ValueError(
+                f"no implied vol for market option(s) {wrong.tolist()} (price outside its "
+                "no-arbitrage bounds, or a non-finite vol); give them iv_weights of 0")
+        surf.set_iv_market(iv, self.iv_weights)
+        self.market_ivs = iv
 
     def _option_arrays(self):
         """The options' strikes and maturities as NumPy arrays, built once (np.array of the
@@ -299,8 +350,12 @@ class DoubleHestonJumpCalibrator:
         surf = self._get_surface()
         if surf is None:
             return np.full(S, INVALID_LOSS)
-        sse, bad, _ = surf.loss_terms(rec, self.N)
-        loss = np.where(bad > 0, INVALID_LOSS, sse / M + pen)
+        if self.objective == "iv":              # weighted mean squared vol error, device-summed
+            sse, bad = surf.loss_terms_iv(rec, self.N)
+            loss = np.where(bad > 0, INVALID_LOSS, sse / self._iv_wsum + pen)
+        else:
+            sse, bad, _ = surf.loss_terms(rec, self.N)
+            loss = np.where(bad > 0, INVALID_LOSS, sse / M + pen)
         if track:
             valid = loss[bad == 0]
             if valid.size:
@@ -316,6 +371,8 @@ class DoubleHestonJumpCalibrator:
         request; the transforms by NumPy, fd_models) unless a subclass replaces loss_batch,
         whose values are then used the same way."""
         X0 = np.atleast_2d(np.asarray(X0, dtype=np.float64))
+        if self.objective == "iv":      # one request of the 14 S points, the difference on the host
+            return fg_from_losses(self, X0)
         native = not _custom_loss(self)
         surf = self._get_surface() if native and len(self.market_options) else None
         if surf is None:
@@ -403,6 +460,9 @@ class DoubleHestonJumpCalibrator:
         GPU, the host checks for finished starts every few iterations); same algorithm and
         stopping rules, with the subspace step rounded differently (csrc/dh_lbfgs.h)."""
         start_time = time.time()
+        if driver == "device" and self.objective != "price":
+            raise ValueError("driver='device' optimises the price objective only; "
+                             "objective='iv' runs driver='scipy'")
         # draw every start's x0 in start order (the only consumer of the global RNG, :256)
         if x0s is None:
             x0s = self.start_points(multi_start, x0)
@@ -552,7 +612,8 @@ def _native_surface(cal, group_starts):
     cls = type(cal)
     if (not isinstance(cal, DoubleHestonJumpCalibrator)
             or cls.fg_batch is not DoubleHestonJumpCalibrator.fg_batch
-            or _custom_loss(cal) or not len(cal.market_options)):
+            or _custom_loss(cal) or not len(cal.market_options)
+            or cal.objective != "price"):      # dh_surface_fg* form the price loss
         return None
     return cal._get_surface()
 
@@ -948,6 +1009,8 @@ def run_starts_device(cal: DoubleHestonJumpCalibrator, x0s, maxiter: int):
     nothing to optimise on the device and take the host driver, which reproduces the
     reference's result for them."""
     n = len(x0s)
+    if getattr(cal, "objective", "price") != "price":
+        raise ValueError("the device-resident L-BFGS-B optimises the price objective only")
     if n == 0:
         return []
     surf = cal._get_surface()
