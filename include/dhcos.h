@@ -212,7 +212,8 @@ int dh_calibrate_lbfgs(dh_ctx* ctx, const dh_surface* s, const double* x0, int S
                        double r, int N, double L, const dh_lb_options* opt, dh_lb_result* out,
                        int32_t* n_launches);
 /* Diagnostics (tests): with cap > 0, dh_calibrate_lbfgs records every consumed request as 40
- * doubles [start, request number, f, x[13], g[13], 0 0 0, 6 phase stamps of the step kernel
+ * doubles [start, request number, f, x[13], g[13], 3 spare (dh_calibrate_lbfgs_batch: the
+ * start's market, then 2 spare), 6 phase stamps of the step kernel
  * (DH_STAMPS build only, else 0) 0 0] (order across starts arbitrary); dh_ctx_read_lb_trace
  * copies up to cap records of the last call and sets *n to the count.                         */
 int dh_ctx_set_lb_trace(dh_ctx* ctx, int64_t cap);
@@ -414,6 +415,45 @@ int dh_surface_loss_iv_dev(dh_ctx* ctx, const dh_surface* s, const double* d_par
  * the optional prices [S][M], iv [S][M] out (NULL to skip either).                              */
 int dh_surface_loss_iv(dh_ctx* ctx, const dh_surface* s, const double* params, int S, int N,
                        double L, double* sse, int32_t* n_bad, double* prices, double* iv);
+
+/* ---- many markets on one option grid (csrc/dh_loss_rows.h) ------------------- */
+/* Replaces the Python loop DoubleHestonJumpCalibrator(spot_b, r_b, options_b).calibrate() over the
+ * rows of the generator's (market [n][15], spots [n]) arrays (lbfgs_calibrator.py:179-299 once
+ * per row).  B markets share the surface's options (its strike mode forms each record's strikes
+ * from the record's own spot, or keeps the listed ones); the surface needs no market prices.
+ * The reduction stage alone, over prices already on the device: d_prices [S][M] as
+ * dh_surface_price_dev writes them, d_mkt [B][M] market prices in the caller's option order,
+ * d_row [S] the market row of each param set (in [0, B); the caller's promise).  Per set s, with
+ * m = d_mkt[d_row[s]*M + .]:
+ *   sse[s]   = sum of ((p - m) / m)^2 over the M options
+ *   n_bad[s] = #{p NaN, +-inf or <= 0}
+ * dh_surface_loss's rules (a zero market price gives inf, a NaN one NaN).  One wave per set: lane
+ * l adds options l, l + 64, ... in order from 0.0, then the xor butterfly over the 64 lanes
+ * (offsets 1, 2, 4, 8, 16, 32); nothing is contracted.  sse[s] depends on nothing but set s's
+ * prices and its market row: the same bits in any request, at any place in it.  Enqueues on
+ * `stream` (NULL = the context's); no synchronisation, no allocation.                           */
+int dh_surface_loss_rows_dev(dh_ctx* ctx, const dh_surface* s, const double* d_prices,
+                             const double* d_mkt, const int32_t* d_row, int S, double* d_sse,
+                             int32_t* d_n_bad, void* stream);
+/* The host-pointer form, synchronous: params [S][16] are priced as dh_surface_price prices them
+ * (the same kernels), then reduced against mkt [B][M] by row [S]; sse [S], n_bad [S] and the
+ * optional prices [S][M] out.  DH_E_ARG for a row outside [0, B).                                */
+int dh_surface_loss_rows(dh_ctx* ctx, const dh_surface* s, const double* params, const double* mkt,
+                         const int32_t* row, int S, int B, int N, double L, double* sse,
+                         int32_t* n_bad, double* prices);
+/* dh_calibrate_lbfgs over many markets at once: start i fits market market_of[i], whose market
+ * prices are mkt[market_of[i]][M], spot spot[market_of[i]] and rate rate[market_of[i]].  Every
+ * iteration is one price launch over the 14 x (live starts) records, the reduction above (each
+ * slot's row taken from its start's market) and one step launch, which writes each next request's
+ * records with that start's spot and rate.  Options, results, chunked enqueue, compaction and the
+ * trace (whose first spare double holds the market index) are dh_calibrate_lbfgs's.  A start's
+ * requests and results depend on nothing but its own x0 and market: not on B, S, the order of the
+ * markets or the chunk size.  DH_E_ARG for M == 0, B <= 0 with S > 0, a market_of entry outside
+ * [0, B), a spot that is not finite or not > 0, a rate that is not finite.                      */
+int dh_calibrate_lbfgs_batch(dh_ctx* ctx, const dh_surface* s, const double* mkt,
+                             const double* spot, const double* rate, int B, const double* x0,
+                             const int32_t* market_of, int S, int N, double L,
+                             const dh_lb_options* opt, dh_lb_result* out, int32_t* n_launches);
 
 /* ---- building blocks (exposed for API parity with the reference's public methods) -------- */
 /* phi(u_j; tau) for one param set: DoubleHeston.characteristic_function (double_heston.py:48-97) */

@@ -2888,6 +2888,9 @@ struct dh_ctx {
     GenBufs* gen = nullptr;    // the generator's device draw (dh_gen_device)
     DevBuf iv;                 // quote columns / vols of dh_implied_vol, dh_surface_implied_vol
     DevBuf iv_part_sse, iv_part_bad;   // tile partials of dh_surface_iv_sse_dev (dh_iv_loss.h)
+    DevBuf rows_mkt, rows_row;         // market rows / row of each set (dh_loss_rows.h)
+    // dh_calibrate_lbfgs_batch: the requests' prices, and each start's spot, rate and market
+    DevBuf lb_prices, lb_spot, lb_rate, lb_mof;
 };
 
 struct dh_surface {
@@ -3441,7 +3444,8 @@ int dh_ctx_destroy(dh_ctx* ctx) {
                       &ctx->aux1, &ctx->aux2, &ctx->aux3, &ctx->pre, &ctx->lb_state, &ctx->lb_rec,
                       &ctx->lb_sse, &ctx->lb_bad, &ctx->lb_live, &ctx->lb_done, &ctx->lb_x0,
                       &ctx->lb_trace, &ctx->lb_trace_n, &ctx->iv, &ctx->iv_part_sse,
-                      &ctx->iv_part_bad})
+                      &ctx->iv_part_bad, &ctx->rows_mkt, &ctx->rows_row, &ctx->lb_prices,
+                      &ctx->lb_spot, &ctx->lb_rate, &ctx->lb_mof})
         b->release();
     ctx->h_params.release();
     ctx->h_loss.release();
@@ -3667,6 +3671,25 @@ int dh_surface_price_dev(dh_ctx* ctx, const dh_surface* s, const double* d_param
 }
 
 }  // extern "C"
+
+// dh_surface_price_dev for the batch driver's requests (dh_calibrate_lbfgs_batch): a no-op once
+// *live_count is 0, and the kernel choice does not follow the request's size -- under
+// DH_PATH_AUTO the fused kernels wherever they apply, so a start's prices have the same bits
+// whatever shares its launch (the generator kernel of large calls rounds differently, 3.3)
+static int surface_price_launch_lb(dh_ctx* ctx, const dh_surface* s, const double* d_params,
+                                   int64_t P, int N, double L, double* d_out, hipStream_t st,
+                                   const int* live_count) {
+    if (P == 0 || s->M == 0) return DH_OK;
+    PriceArgs A = surface_args(s, d_params, P, N, L);
+    A.exact = per_term(ctx, N);
+    A.out = d_out;
+    A.live_count = live_count;
+    const int path = ctx->path;
+    if (path == DH_PATH_AUTO) ctx->path = DH_PATH_FUSED;
+    const int rc = launch_price(ctx, A, st);
+    ctx->path = path;
+    return rc;
+}
 
 static int surface_loss_launch(dh_ctx* ctx, const dh_surface* s, const double* d_params, int S,
                                int N, double L, double* d_sse, int32_t* d_n_bad,
@@ -4177,6 +4200,13 @@ struct LbArgs {
     int n_tiles;
     int n_inline;              // live list passed by value below (saves a dependent load), or 0
     int live_inline[kLbInline];
+    // dh_calibrate_lbfgs_batch only (lb_step_kernel<., true>), appended so that nothing above
+    // moves: each start's spot, rate and market, and the market row of every set of the next
+    // request (what dh_loss_rows.h's reduction reads)
+    const double* spot_of;     // [S]
+    const double* rate_of;     // [S]
+    const int* market_of;      // [S]
+    int* row;                  // [n_live * 14]
 };
 static_assert(std::is_standard_layout<LbArgs>::value, "lb_live_inline reads LbArgs by offset");
 
@@ -4230,9 +4260,11 @@ __device__ __forceinline__ double lb_transform(int i, double x) {
 // scipy/optimize/_numdiff.py:498-511); lane i maps x_i and lane 16 + i maps x_i + h_i to a model
 // param (one transform per lane), lane i keeps dx_i = (x_i + h_i) - x_i; lane t < 14 assembles
 // point t (x, or x + h_{t-1} e_{t-1}), writes its record and keeps its Feller penalty
-// (lbfgs_calibrator.py:113-116) in pen.
+// (lbfgs_calibrator.py:113-116) in pen.  kB (the multi-market driver): the record carries start
+// sidx's own spot and rate, and the set's market row is written beside it.
+template <bool kB>
 __device__ void lb_emit(const WaveCore& c, WaveVec& dx, WaveVec& pen, double* pb, double* pp,
-                        const LbArgs& A, int slot, int lane) {
+                        const LbArgs& A, int slot, int lane, [[maybe_unused]] int sidx) {
     const int i = lane & 15;
     const double xi = c.xe.v;                       // every row holds xe
     double h = kFdStep;
@@ -4256,8 +4288,14 @@ __device__ void lb_emit(const WaveCore& c, WaveVec& dx, WaveVec& pen, double* pb
         double* out = A.rec + ((size_t)slot * dhlb::kPts + lane) * DH_PARAM_STRIDE;
 #pragma unroll
         for (int i = 0; i < dhlb::kN; ++i) out[i] = p[i];
-        out[13] = A.S0;
-        out[14] = A.r;
+        if constexpr (kB) {
+            out[13] = A.spot_of[sidx];
+            out[14] = A.rate_of[sidx];
+            A.row[(size_t)slot * dhlb::kPts + lane] = A.market_of[sidx];
+        } else {
+            out[13] = A.S0;
+            out[14] = A.r;
+        }
         out[15] = 0.0;
     }
 }
@@ -4302,8 +4340,10 @@ __device__ __forceinline__ void lb_tile_tree(const double* ps, int nt, double& s
 // One wave per live start: load the state (vectors into registers, lane i = component i; the
 // pair memory into LDS), consume the finished request (lane t forms loss t, lane i gradient
 // component i), run the L-BFGS-B state machine until it needs a new point, emit that request,
-// store the state.
-template <bool kPre>
+// store the state.  kB: dh_calibrate_lbfgs_batch's build -- the emitted records carry the start's
+// own spot and rate (lb_emit<true>) and the trace's first spare double the start's market; the
+// two kB = false builds are dh_calibrate_lbfgs's, unchanged.
+template <bool kPre, bool kB = false>
 __global__ __launch_bounds__(64) void lb_step_kernel(
     LbSlot* __restrict__ h_states, const double* __restrict__ h_part, int h_ntiles, int h_mode,
     int h_part_mode, int h_l0, int h_l1, int h_l2, int h_l3, LbArgs A_) {
@@ -4407,6 +4447,7 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
                     tr[0] = sidx;
                     tr[1] = c.s.n_calls / dhlb::kPts - 1;
                     tr[2] = c.s.fe;
+                    if constexpr (kB) tr[3 + 2 * dhlb::kN] = A.market_of[sidx];
                 }
                 if (lane < dhlb::kN) {
                     tr[3 + lane] = c.xe.v;
@@ -4425,7 +4466,7 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
             atomicSub(A.live_count, 1);
         }
     }
-    if (need) lb_emit(c, dx, pen, pb, pp, A, slot, lane);
+    if (need) lb_emit<kB>(c, dx, pen, pb, pp, A, slot, lane, sidx);
     __syncthreads();
     [[maybe_unused]] const unsigned long long t_emit = lb_clock();
     {   // every LDS read before the first store (one LDS round trip, not one per store)
@@ -4456,7 +4497,22 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
 #endif
 }
 
-int launch_lb_step(hipStream_t st, const LbArgs& A, int n_live) {
+int launch_lb_step(hipStream_t st, const LbArgs& A, int n_live, bool batch = false) {
+    if (batch) {
+        if (A.n_inline && n_live <= kLbPre) {
+            int l[kLbPre] = {0, 0, 0, 0};
+            for (int i = 0; i < n_live; ++i) l[i] = A.live_inline[i];
+            hipLaunchKernelGGL((lb_step_kernel<true, true>), dim3((unsigned)n_live), dim3(64), 0,
+                               st, A.states, A.part_sse, A.n_tiles, A.mode, A.part_mode, l[0],
+                               l[1], l[2], l[3], A);
+        } else {
+            hipLaunchKernelGGL((lb_step_kernel<false, true>), dim3((unsigned)n_live), dim3(64), 0,
+                               st, A.states, A.part_sse, A.n_tiles, A.mode, A.part_mode, 0, 0, 0,
+                               0, A);
+        }
+        HIP_TRY(hipGetLastError());
+        return DH_OK;
+    }
     if (A.n_inline && n_live <= kLbPre) {
         int l[kLbPre] = {0, 0, 0, 0};
         for (int i = 0; i < n_live; ++i) l[i] = A.live_inline[i];
@@ -4470,13 +4526,27 @@ int launch_lb_step(hipStream_t st, const LbArgs& A, int n_live) {
     return DH_OK;
 }
 
+// the markets of dh_calibrate_lbfgs_batch (host arrays): mkt [B][M], spot [B], rate [B] and the
+// market of each start
+struct LbBatch {
+    const double* mkt;
+    const double* spot;
+    const double* rate;
+    int B;
+    const int32_t* market_of;
+};
+
 }  // namespace
 
-extern "C" int dh_calibrate_lbfgs(dh_ctx* ctx, const dh_surface* s, const double* x0, int S,
-                                  double S0, double r, int N, double L, const dh_lb_options* opt,
-                                  dh_lb_result* out, int32_t* n_launches) {
+#include "dh_loss_rows.h"
+
+// dh_calibrate_lbfgs (bt null: one market, the surface's, through the fused loss launches) and
+// dh_calibrate_lbfgs_batch (bt: a market per start, through price + dh_loss_rows.h's reduction)
+static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, double S0, double r,
+                  int N, double L, const dh_lb_options* opt, dh_lb_result* out,
+                  int32_t* n_launches, const LbBatch* bt) {
     if (!ctx || !s || !opt || (S > 0 && (!x0 || !out))) return fail(DH_E_ARG, "null argument");
-    if (!s->has_mkt) return fail(DH_E_ARG, "surface has no market prices");
+    if (!bt && !s->has_mkt) return fail(DH_E_ARG, "surface has no market prices");
     if (s->M == 0) return fail(DH_E_ARG, "empty market (the loss is NaN; no optimisation)");
     int rc = check_N(N);
     if (rc) return rc;
@@ -4484,6 +4554,21 @@ extern "C" int dh_calibrate_lbfgs(dh_ctx* ctx, const dh_surface* s, const double
     if (opt->maxiter < 0 || opt->maxfun < 0 || opt->maxls < 1)   // SciPy: maxls must be > 0
         return fail(DH_E_ARG, "maxiter and maxfun must be >= 0, maxls >= 1");
     if (n_launches) *n_launches = 0;
+    if (bt) {
+        if (S > 0 && bt->B <= 0) return fail(DH_E_ARG, "B <= 0");
+        if (bt->B > 0 && (!bt->mkt || !bt->spot || !bt->rate))
+            return fail(DH_E_ARG, "null argument");
+        if (S > 0 && !bt->market_of) return fail(DH_E_ARG, "null argument");
+        for (int b = 0; b < bt->B; ++b) {
+            if (!std::isfinite(bt->spot[b]) || !(bt->spot[b] > 0.0))
+                return fail(DH_E_ARG, "spot " + std::to_string(b) + " is not finite or not > 0");
+            if (!std::isfinite(bt->rate[b]))
+                return fail(DH_E_ARG, "rate " + std::to_string(b) + " is not finite");
+        }
+        for (int i = 0; i < S; ++i)
+            if (bt->market_of[i] < 0 || bt->market_of[i] >= bt->B)
+                return fail(DH_E_ARG, "market_of " + std::to_string(i) + " is outside [0, B)");
+    }
     if (S == 0) return DH_OK;
     DeviceScope dev_scope(ctx->device);
     if (dev_scope.rc) return dev_scope.rc;
@@ -4507,6 +4592,29 @@ extern "C" int dh_calibrate_lbfgs(dh_ctx* ctx, const dh_surface* s, const double
     HIP_TRY(hipMemcpyAsync(ctx->lb_x0.ptr, x0, (size_t)S * dhlb::kN * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ctx->lb_live.ptr, h_live[0], (size_t)S * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ctx->lb_done.ptr, S, 1, st));
+    const int M = s->M;
+    if (bt) {
+        // each start's spot and rate gathered on the host: one load per emitted record
+        const size_t mb = (size_t)bt->B * M * 8;
+        HIP_TRY(ctx->rows_mkt.reserve(mb));
+        HIP_TRY(ctx->rows_row.reserve(npts * 4));
+        HIP_TRY(ctx->lb_prices.reserve(npts * M * 8));
+        HIP_TRY(ctx->lb_spot.reserve((size_t)S * 8));
+        HIP_TRY(ctx->lb_rate.reserve((size_t)S * 8));
+        HIP_TRY(ctx->lb_mof.reserve((size_t)S * 4));
+        std::vector<double> sr((size_t)2 * S);
+        for (int i = 0; i < S; ++i) {
+            sr[i] = bt->spot[bt->market_of[i]];
+            sr[(size_t)S + i] = bt->rate[bt->market_of[i]];
+        }
+        HIP_TRY(hipMemcpyAsync(ctx->rows_mkt.ptr, bt->mkt, mb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->lb_spot.ptr, sr.data(), (size_t)S * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->lb_rate.ptr, sr.data() + S, (size_t)S * 8,
+                               hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->lb_mof.ptr, bt->market_of, (size_t)S * 4, hipMemcpyHostToDevice,
+                               st));
+        HIP_TRY(hipStreamSynchronize(st));            // `sr` is pageable and leaves scope
+    }
     if (!ctx->lb_ev[0]) {
         for (hipEvent_t& e : ctx->lb_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
@@ -4544,12 +4652,17 @@ extern "C" int dh_calibrate_lbfgs(dh_ctx* ctx, const dh_surface* s, const double
     A.part_mode = 0;
     A.part_sse = nullptr;
     A.n_tiles = s->n_tiles;
+    A.spot_of = bt ? (const double*)ctx->lb_spot.ptr : nullptr;
+    A.rate_of = bt ? (const double*)ctx->lb_rate.ptr : nullptr;
+    A.market_of = bt ? (const int*)ctx->lb_mof.ptr : nullptr;
+    A.row = bt ? (int*)ctx->rows_row.ptr : nullptr;
+    const bool batch = bt != nullptr;
     auto set_inline = [&](const int* lst, int n) {
         A.n_inline = n <= kLbInline ? 1 : 0;
         for (int i = 0; i < kLbInline; ++i) A.live_inline[i] = i < n && A.n_inline ? lst[i] : 0;
     };
     set_inline(h_live[0], S);
-    rc = launch_lb_step(st, A, S);
+    rc = launch_lb_step(st, A, S, batch);
     if (rc) return rc;
 
     // Chunks of `chunk` iterations (loss launch(es) + step launch) are enqueued two ahead of the
@@ -4572,8 +4685,25 @@ extern "C" int dh_calibrate_lbfgs(dh_ctx* ctx, const dh_surface* s, const double
     auto enqueue_chunk = [&](int k) -> int {
         A.mode = 1;
         for (int c = 0; c < chunk; ++c) {
-            int e = surface_loss_launch(ctx, s, A.rec, n_live * dhlb::kPts, N, L, (double*)A.sse,
-                                        (int32_t*)A.bad, nullptr, st, A.live_count, true);
+            int e;
+            if (batch) {
+                // prices of the 14 x live records, then each set against its start's market row
+                // (the rows the step kernel wrote beside the records)
+                e = surface_price_launch_lb(ctx, s, A.rec, (int64_t)n_live * dhlb::kPts, N, L,
+                                            (double*)ctx->lb_prices.ptr, st, A.live_count);
+                if (e) return e;
+                e = loss_rows_launch(ctx, s, (const double*)ctx->lb_prices.ptr,
+                                     (const double*)ctx->rows_mkt.ptr, (const int32_t*)A.row,
+                                     n_live * dhlb::kPts, (double*)A.sse, (int32_t*)A.bad, st,
+                                     A.live_count);
+                if (e) return e;
+                e = launch_lb_step(st, A, n_live, true);     // part_mode 0: reads sse / bad
+                if (e) return e;
+                ++launches;
+                continue;
+            }
+            e = surface_loss_launch(ctx, s, A.rec, n_live * dhlb::kPts, N, L, (double*)A.sse,
+                                    (int32_t*)A.bad, nullptr, st, A.live_count, true);
             if (e) return e;
             // a fused request stored its tile partials only (no hand-off): the step sums them
             A.part_mode = !per_term(ctx, N) && ctx->last_path == DH_PATH_FUSED ? 1 : 0;
@@ -4624,7 +4754,7 @@ extern "C" int dh_calibrate_lbfgs(dh_ctx* ctx, const dh_surface* s, const double
                                        hipMemcpyHostToDevice, st));
             }
             A.mode = 2;
-            rc = launch_lb_step(st, A, n_live);
+            rc = launch_lb_step(st, A, n_live, batch);
             if (rc) return rc;
         }
         rc = enqueue_chunk(k + 2);
@@ -4651,6 +4781,21 @@ extern "C" int dh_calibrate_lbfgs(dh_ctx* ctx, const dh_surface* s, const double
     }
     if (n_launches) *n_launches = (int32_t)launches;
     return DH_OK;
+}
+
+extern "C" int dh_calibrate_lbfgs(dh_ctx* ctx, const dh_surface* s, const double* x0, int S,
+                                  double S0, double r, int N, double L, const dh_lb_options* opt,
+                                  dh_lb_result* out, int32_t* n_launches) {
+    return lb_run(ctx, s, x0, S, S0, r, N, L, opt, out, n_launches, nullptr);
+}
+
+extern "C" int dh_calibrate_lbfgs_batch(dh_ctx* ctx, const dh_surface* s, const double* mkt,
+                                        const double* spot, const double* rate, int B,
+                                        const double* x0, const int32_t* market_of, int S, int N,
+                                        double L, const dh_lb_options* opt, dh_lb_result* out,
+                                        int32_t* n_launches) {
+    const LbBatch bt{mkt, spot, rate, B, market_of};
+    return lb_run(ctx, s, x0, S, 0.0, 0.0, N, L, opt, out, n_launches, &bt);
 }
 
 extern "C" int dh_ctx_set_lb_trace(dh_ctx* ctx, int64_t cap) {

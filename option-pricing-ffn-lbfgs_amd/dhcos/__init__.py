@@ -7,6 +7,7 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
     CalibrationResult
     generate_synthetic_calibrations   src/data/synthetic_generator.py
     implied_vol                       (new: Black-Scholes implied volatility of prices)
+    calibrate_batch                   (new: many markets on one option grid, calibrated together)
 
 All pricing arithmetic runs in libdhcos.so (hand-written gfx950 HIP kernels, C-ABI in
 include/dhcos.h); the native library is loaded on first use and there is no CPU fallback.
@@ -17,8 +18,10 @@ torch) shards starts / samples over ``torch.distributed`` ranks (one process per
 from .pricer import DoubleHeston, implied_vol
 from .calibrator import CalibrationResult, DoubleHestonJumpCalibrator
 from .generator import generate_synthetic_calibrations
+from .batch import BatchCalibrationResult, calibrate_batch
 from ._native import NativeError
 
 __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
-           "generate_synthetic_calibrations", "implied_vol", "NativeError"]
+           "generate_synthetic_calibrations", "implied_vol", "NativeError", "calibrate_batch",
+           "BatchCalibrationResult"]
 __version__ = "0.1.0"

@@ -129,7 +129,13 @@ SIGNATURES = {
                                          _vp, _vp, _vp]),
     "dh_surface_loss_iv": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp,
                                      _vp]),
-    "dh_cf": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, _dp, _dp]),
+    "dh_surface_loss_rows_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "dh_surface_loss_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                       C.c_double, _vp, _vp, _vp]),
+    "dh_calibrate_lbfgs_batch": (C.c_int, [_vp, _vp, _dp, _dp, _dp, C.c_int, _dp, _i32p, C.c_int,
+                                           C.c_int, C.c_double, C.POINTER(LbOptions),
+                                           C.POINTER(LbResult), _i32p]),
+    "dh_cf":(C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, _dp, _dp]),
     "dh_cf_complex": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp]),
     "dh_trunc_range": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int64, C.c_double, _dp, _dp]),
     "dh_cos_coeffs": (C.c_int, [_vp, _i32p, C.c_int, C.c_double, C.c_double, C.c_double,
@@ -448,6 +454,32 @@ class Context:
         return chi, psi
 
 
+def lb_batch_args(M, mkt, spots, rates, x0s, market_of):
+    """The arguments of dh_calibrate_lbfgs_batch as contiguous arrays, checked as the library
+    checks them (shapes here, values there too): -> (mkt [B, M], spots [B], rates [B],
+    x0s [S, 13], market_of [S] int32), or ValueError."""
+    mkt = _f64(mkt)
+    if mkt.ndim != 2 or mkt.shape[1] != M:
+        raise ValueError(f"mkt must be [B, {M}], got {mkt.shape}")
+    B = mkt.shape[0]
+    spots = _f64(spots).reshape(-1)
+    rates = _f64(rates).reshape(-1)
+    if spots.size != B or rates.size != B:
+        raise ValueError("mkt, spots and rates differ in length")
+    if not (np.all(np.isfinite(spots)) and np.all(spots > 0)):
+        raise ValueError("every spot must be finite and > 0")
+    if not np.all(np.isfinite(rates)):
+        raise ValueError("every rate must be finite")
+    x0s = _f64(x0s).reshape(-1, 13)
+    S = x0s.shape[0]
+    mof = np.asarray(market_of).reshape(-1)
+    if mof.size != S:
+        raise ValueError("x0s and market_of differ in length")
+    if S and (mof.dtype.kind not in "iu" or mof.min() < 0 or mof.max() >= B):
+        raise ValueError(f"market_of must hold integers in [0, {B})")
+    return mkt, spots, rates, x0s, np.ascontiguousarray(mof, dtype=np.int32)
+
+
 class Surface:
     """An option set resident in HBM, grouped by maturity into <=256-option tiles (dh_surface)."""
 
@@ -547,6 +579,55 @@ class Surface:
             _check(load().dh_calibrate_lbfgs(ctx.handle, self._h, _ptr(x0s), S, float(S0),
                                              float(r), int(N), float(L), C.byref(opt), res,
                                              C.byref(nl)))
+        return list(res)[:S], nl.value
+
+    def loss_terms_rows(self, params, mkt, row, N=128, L=10.0, want_prices=False):
+        """dh_surface_loss_rows -> (sse[S], n_bad[S], prices[S,M] or None): the squared relative
+        price errors of every param row against row mkt[row[s]] of the market prices mkt [B, M]
+        (the surface's option order), and the count of invalid prices."""
+        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        S = params.shape[0]
+        mkt = _f64(mkt).reshape(-1, self.M) if self.M else _f64(mkt).reshape(len(mkt), 0)
+        B = mkt.shape[0]
+        row = np.ascontiguousarray(row, dtype=np.int32).reshape(-1)
+        if row.size != S:
+            raise ValueError("params and row differ in length")
+        sse = np.empty(S)
+        bad = np.empty(S, dtype=np.int32)
+        prices = np.empty((S, self.M)) if want_prices else None
+        with self.ctx._lock:
+            _check(load().dh_surface_loss_rows(self.ctx.handle, self._h, params.ctypes.data,
+                                               mkt.ctypes.data, row.ctypes.data, S, B, int(N),
+                                               float(L), sse.ctypes.data, bad.ctypes.data,
+                                               None if prices is None else prices.ctypes.data))
+        return sse, bad, prices
+
+    def loss_rows_dev(self, d_prices: int, d_mkt: int, d_row: int, S: int, d_sse: int, d_bad: int,
+                      stream: int = 0):
+        """dh_surface_loss_rows_dev: the per-row reduction over [S, M] prices on the device."""
+        _check(load().dh_surface_loss_rows_dev(self.ctx.handle, self._h, _vp(d_prices),
+                                               _vp(d_mkt), _vp(d_row), int(S), _vp(d_sse),
+                                               _vp(d_bad), _vp(stream) if stream else None))
+
+    def calibrate_lbfgs_batch(self, mkt, spots, rates, x0s, market_of, N=128, L=10.0, *,
+                              maxiter=300, maxfun=15000, maxls=20, ftol=1e-9, gtol=1e-6, chunk=8,
+                              ctx=None):
+        """Device-resident L-BFGS-B over many markets on this surface's option grid
+        (dh_calibrate_lbfgs_batch): row i of x0s [S, 13] fits market market_of[i] -- market
+        prices mkt[b] of mkt [B, M], spot spots[b], rate rates[b].
+        -> (list of LbResult, number of iterations enqueued)."""
+        ctx = ctx or self.ctx
+        mkt, spots, rates, x0s, mof = lb_batch_args(self.M, mkt, spots, rates, x0s, market_of)
+        B, S = mkt.shape[0], x0s.shape[0]
+        opt =LbOptions(int(maxiter), int(maxfun), int(maxls), int(chunk), float(ftol),
+                        float(gtol))
+        res = (LbResult * max(S, 1))()
+        nl = C.c_int32(0)
+        with ctx._lock:
+            _check(load().dh_calibrate_lbfgs_batch(ctx.handle, self._h, _ptr(mkt), _ptr(spots),
+                                                   _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p),
+                                                   S, int(N), float(L), C.byref(opt), res,
+                                                   C.byref(nl)))
         return list(res)[:S], nl.value
 
     def fg(self, X0, S0, r, N=128, L=10.0, model=None):
@@ -1214,4 +1295,4 @@ __all__ = ["gen_draw", "gen_assemble", "gen_dates", "gen_locate", "gen_draw_loca
            "SIGNATURES",
            "Comm", "comm_id", "best_start", "COMM_ID_BYTES", "FgChannel", "pinned",
            "pinned_empty", "host_cache_trim", "gen_device", "gen_log",
-           "math_probe", "MATH_PROBE_FNS"]
+           "math_probe", "MATH_PROBE_FNS", "lb_batch_args"]

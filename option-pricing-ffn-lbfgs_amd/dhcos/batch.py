@@ -1,0 +1,292 @@
+"""``calibrate_batch``: many markets on one option grid, calibrated together on the device.
+
+The reference's pipeline is generator -> FFN -> L-BFGS refinement of the FFN's guess, sample after
+sample (lbfgs_calibrator.py:236-336 once per sample).  Here B markets that share one option grid
+-- strikes in percent of each market's spot (the generator's grid), or one listed absolute grid
+under moving spots -- run every start of every market through the same launches
+(dh_calibrate_lbfgs_batch): each iteration prices the 14 points of every live
+start's pending request in one launch, reduces each against its own market's prices and advances
+every start's L-BFGS-B state.  A start's trajectory depends on its own x0 and market alone, so a
+market's result does not depend on what else is in the batch.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+from scipy.optimize._lbfgsb_py import status_messages, task_messages
+
+from . import _native
+from .calibrator import (_MAXFUN, N_PARAMS, PARAM_NAMES, CalibrationResult,
+                         DoubleHestonJumpCalibrator, x_to_model)
+from .generator import MATURITIES, STRIKES_PCT, grid_surface
+from .pricer import resolve_call
+
+FAILED_MESSAGE = "All optimization starts failed"      # lbfgs_calibrator.py:318-333
+
+
+def task_message(task: int) -> str:
+    """SciPy's message for a task code status * 1000 + message (dh_lb_result.task)."""
+    return status_messages[int(task) // 1000] + ": " + task_messages[int(task) % 1000]
+
+
+def pick_winners(fun) -> np.ndarray:
+    """best start per market of fun [B, S]: the first start, in start order, whose fun is strictly
+    below every earlier one's and below inf (lbfgs_calibrator.py:271-275, dh_best_start's rule);
+    NaN never wins; -1 where no start qualifies."""
+    fun = np.asarray(fun, dtype=np.float64)
+    if fun.ndim != 2:
+        raise ValueError(f"fun must be [B, S], got {fun.shape}")
+    B, S = fun.shape
+    if S == 0:
+        return np.full(B, -1, dtype=np.int64)
+    f = np.where(np.isnan(fun), np.inf, fun)
+    best = np.argmin(f, axis=1)                        # the first occurrence of the minimum
+    return np.where(f[np.arange(B), best] < np.inf, best, -1)
+
+
+@dataclass
+class BatchCalibrationResult:
+    """calibrate_batch's result: arrays over markets [B] and over starts [B, S]."""
+    spots: np.ndarray            # [B]
+    risk_free: np.ndarray        # [B]
+    market_prices: np.ndarray    # [B, M]
+    strikes: np.ndarray          # [B, M] absolute strikes of each market
+    maturities: np.ndarray       # [M]
+    is_call: np.ndarray          # [M] bool
+    # per market (the winning start; the reference's failure row where none wins)
+    parameters: np.ndarray       # [B, 13] model parameters
+    x: np.ndarray                # [B, 13] unconstrained
+    final_loss: np.ndarray       # [B]
+    iterations: np.ndarray       # [B]
+    success: np.ndarray          # [B] bool
+    task: np.ndarray             # [B] SciPy task code of the winner (0 where none)
+    best_start: np.ndarray       # [B] (-1 where none)
+    model_prices: np.ndarray     # [B, M]
+    calibration_time: np.ndarray   # [B] seconds until the host saw the winner finish
+    # per start
+    fun: np.ndarray              # [B, S]
+    nit: np.ndarray              # [B, S]
+    nfev: np.ndarray             # [B, S]
+    start_task: np.ndarray       # [B, S]
+    status: np.ndarray           # [B, S] SciPy warnflag
+    best_loss: np.ndarray        # [B, S]
+    n_calls: np.ndarray          # [B, S]
+    start_x: np.ndarray          # [B, S, 13]
+    iterations_enqueued: int = 0
+
+    def message(self, b: int) -> str:
+        return task_message(self.task[b]) if self.best_start[b] >= 0 else FAILED_MESSAGE
+
+    def market_options(self, b: int):
+        return [{"strike": float(k), "maturity": float(t), "price": float(p),
+                 "option_type": "call" if c else "put"}
+                for k, t, p, c in zip(self.strikes[b], self.maturities, self.market_prices[b],
+                                      self.is_call)]
+
+    def result(self, b: int) -> CalibrationResult:
+        """Market b as the reference's CalibrationResult (lbfgs_calibrator.py:21-41)."""
+        b = int(b)
+        return CalibrationResult(
+            date="", spot=float(self.spots[b]), risk_free=float(self.risk_free[b]),
+            parameters={n: float(v) for n, v in zip(PARAM_NAMES, self.parameters[b])},
+            market_prices=self.market_prices[b].copy(), model_prices=self.model_prices[b].copy(),
+            market_options=self.market_options(b), final_loss=float(self.final_loss[b]),
+            calibration_time=float(self.calibration_time[b]), success=bool(self.success[b]),
+            iterations=int(self.iterations[b]), message=self.message(b))
+
+
+def _grid(strikes_pct, maturities, strikes, is_call):
+    """-> (K [M] in grid order (T outer, K inner), T [M], flags [M] bool, strike mode)."""
+    if strikes is not None:
+        k, mode = np.asarray(strikes, dtype=np.float64).reshape(-1), _native.STRIKE_ABSOLUTE
+    else:
+        k, mode = np.asarray(strikes_pct, dtype=np.float64).reshape(-1), _native.STRIKE_PCT_SPOT
+    t = np.asarray(maturities, dtype=np.float64).reshape(-1)
+    K, T = np.tile(k, t.size), np.repeat(t, k.size)
+    if K.size == 0:
+        raise ValueError("the option grid is empty")
+    if not (np.all(np.isfinite(K)) and np.all(K > 0) and np.all(np.isfinite(T)) and np.all(T > 0)):
+        raise ValueError("strikes and maturities must be finite and positive")
+    if isinstance(is_call, str):
+        flags = np.full(K.size, resolve_call(is_call), dtype=bool)
+    else:
+        flags = np.asarray(is_call)
+        if flags.dtype.kind not in "biu":
+            raise ValueError("is_call must be a bool, or bools per option")
+        flags = flags.astype(bool)
+        if flags.ndim == 0:
+            flags = np.full(K.size, bool(flags))
+        elif flags.shape != (K.size,):
+            raise ValueError(f"is_call must be a scalar or [{K.size}], got {flags.shape}")
+    return K, T, flags, mode
+
+
+def check_markets(market_prices, spots, risk_free, M):
+    """-> (market [B, M], spots [B], rates [B]) as float64, or ValueError."""
+    mkt = np.ascontiguousarray(market_prices, dtype=np.float64)
+    if mkt.ndim != 2 or mkt.shape[1] != M:
+        raise ValueError(f"market_prices must be [B, {M}], got {mkt.shape}")
+    B = mkt.shape[0]
+    sp = np.ascontiguousarray(spots, dtype=np.float64)
+    if sp.shape != (B,):
+        raise ValueError(f"spots must be [{B}], got {sp.shape}")
+    if not (np.all(np.isfinite(sp)) and np.all(sp > 0)):
+        raise ValueError("every spot must be finite and > 0")
+    r = np.asarray(risk_free, dtype=np.float64)
+    if r.ndim == 0:
+        r = np.full(B, float(r))
+    elif r.shape != (B,):
+        raise ValueError(f"risk_free must be a scalar or [{B}], got {r.shape}")
+    if not np.all(np.isfinite(r)):
+        raise ValueError("every rate must be finite")
+    return mkt, sp, np.ascontiguousarray(r)
+
+
+def _options(b, mkt, sp, Kabs, T, flags):
+    return [{"strike": Kabs[b, j], "maturity": T[j], "price": mkt[b, j],
+             "option_type": "call" if flags[j] else "put"} for j in range(T.size)]
+
+
+def default_starts(mkt, sp, r, Kabs, T, flags, multi_start):
+    """The starts a loop of calibrate() calls over the markets would draw, in market order:
+    DoubleHestonJumpCalibrator(spot_b, r_b, options_b).start_points(multi_start) -- the only
+    consumer of the global RNG, consumed exactly as that loop consumes it.  -> [B, S, 13]."""
+    B, S = mkt.shape[0], int(multi_start)
+    out = np.empty((B, S, N_PARAMS))
+    for b in range(B):
+        cal = DoubleHestonJumpCalibrator(float(sp[b]), float(r[b]),
+                                         _options(b, mkt, sp, Kabs, T, flags))
+        pts = cal.start_points(S)
+        if S:
+            out[b] = np.stack(pts)
+    return out
+
+
+def resolve_starts(x0s, B):
+    """x0s as [B, S, 13] unconstrained: an array of that shape, or [B][S] dicts of the 13 model
+    parameters (an FFN's output), mapped as inverse_transform_params maps them."""
+    rows = list(x0s) if not isinstance(x0s, np.ndarray) else x0s
+    if len(rows) != B:
+        raise ValueError(f"x0s must hold {B} markets, got {len(rows)}")
+    flat = [e for row in rows for e in (row if not isinstance(row, dict) else [row])]
+    n_dict = sum(isinstance(e, dict) for e in flat)
+    if n_dict and n_dict != len(flat):
+        raise ValueError("x0s mixes parameter dicts and arrays")
+    if n_dict:
+        if any(isinstance(row, dict) for row in rows):
+            raise ValueError("x0s of dicts must be [B][S]: a list of starts per market")
+        S = len(rows[0])
+        if any(len(row) != S for row in rows):
+            raise ValueError("every market needs the same number of starts")
+        out = np.empty((B, S, N_PARAMS))
+        for b, row in enumerate(rows):
+            for s, d in enumerate(row):
+                missing = [n for n in PARAM_NAMES if n not in d]
+                if missing:
+                    raise ValueError(f"x0s[{b}][{s}] lacks {missing}")
+                out[b, s] = DoubleHestonJumpCalibrator.inverse_transform_params(None, d)
+        return out
+    try:
+        arr = np.ascontiguousarray(x0s, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"x0s must be [B, S, 13] numbers or [B][S] dicts: {e}") from None
+    if arr.ndim != 3 or arr.shape[0] != B or arr.shape[2] != N_PARAMS:
+        raise ValueError(f"x0s must be [{B}, S, {N_PARAMS}], got {arr.shape}")
+    return arr
+
+
+def _surface(ctx, K, T, flags, mode, strikes_pct, maturities):
+    if mode == _native.STRIKE_PCT_SPOT and flags.all():
+        return grid_surface(ctx, strikes_pct, maturities)[0]       # the generator's cached grid
+    grids = ctx.__dict__.setdefault("_batch_surfaces", {})
+    key = (K.tobytes(), T.tobytes(), flags.tobytes(), mode)
+    surf = grids.get(key)
+    if surf is None:
+        surf = grids[key] = _native.Surface(ctx, K, T, flags.astype(np.int8), strike_mode=mode)
+    return surf
+
+
+def summarize(mkt, sp, r, Kabs, T, flags, X, fun, nit, nfev, task, status, best_loss, n_calls,
+              t_done, model_prices_of, enqueued=0) -> BatchCalibrationResult:
+    """Per-market rows from per-start results [B, S]: the winner of each market
+    (pick_winners), re-priced by model_prices_of(params [W, 13], markets [W]) -> [W, M] in one
+    call; a market without a winner gets the reference's failure row (zeros, inf, success
+    False)."""
+    B, M = mkt.shape
+    best = pick_winners(fun)
+    won = np.flatnonzero(best >= 0)
+    bw = best[won]
+    x = np.zeros((B, N_PARAMS))
+    params = np.zeros((B, N_PARAMS))
+    final = np.full(B, np.inf)
+    iters = np.zeros(B, dtype=np.int64)
+    ok = np.zeros(B, dtype=bool)
+    wtask = np.zeros(B, dtype=np.int64)
+    model = np.zeros((B, M))
+    ctime = np.zeros(B)
+    if won.size:
+        x[won] = X[won, bw]
+        params[won] = x_to_model(x[won])
+        final[won] = fun[won, bw]
+        iters[won] = nit[won, bw]
+        ok[won] = status[won, bw] == 0
+        wtask[won] = task[won, bw]
+        ctime[won] = t_done[won, bw]
+        model[won] = model_prices_of(params[won], won)
+    return BatchCalibrationResult(
+        spots=sp, risk_free=r, market_prices=mkt, strikes=Kabs, maturities=T, is_call=flags,
+        parameters=params, x=x, final_loss=final, iterations=iters, success=ok, task=wtask,
+        best_start=best, model_prices=model, calibration_time=ctime, fun=fun, nit=nit, nfev=nfev,
+        start_task=task, status=status, best_loss=best_loss, n_calls=n_calls, start_x=X,
+        iterations_enqueued=enqueued)
+
+
+def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
+                    maturities=MATURITIES, strikes=None, is_call=True, x0s=None, multi_start=3,
+                    maxiter=300, N=128, device=None, chunk=8) -> BatchCalibrationResult:
+    """Calibrate B markets that share one option grid, all starts of all markets together in the
+    device-resident L-BFGS-B.
+
+    market_prices [B, M] in grid order (maturity outer, strike inner -- the generator's), spots
+    [B], risk_free a scalar or [B].  The grid is strikes_pct x maturities (strikes in percent of
+    each market's spot), or strikes x maturities (absolute, the same for every market).
+    x0s: [B, S, 13] unconstrained start points, [B][S] dicts of the 13 model parameters, or None
+    for each market's start_points(multi_start) (the global RNG is consumed as a loop of
+    calibrate() calls over the markets would consume it)."""
+    K, T, flags, mode = _grid(strikes_pct, maturities, strikes, is_call)
+    mkt, sp, r = check_markets(market_prices, spots, risk_free, K.size)
+    B = mkt.shape[0]
+    Kabs = (K[None, :] * sp[:, None] / 100.0 if mode == _native.STRIKE_PCT_SPOT
+            else np.broadcast_to(K, (B, K.size)).copy())
+    if x0s is None:
+        if int(multi_start) < 0:
+            raise ValueError("multi_start < 0")
+        X = default_starts(mkt, sp, r, Kabs, T, flags, multi_start)
+    else:
+        X = resolve_starts(x0s, B)
+    S = X.shape[1]
+    ctx = _native.default_context(device)
+    surf = _surface(ctx, K, T, flags, mode, strikes_pct, maturities)
+    market_of = np.repeat(np.arange(B, dtype=np.int32), S)
+    res, enqueued = surf.calibrate_lbfgs_batch(mkt, sp, r, X.reshape(B * S, N_PARAMS), market_of,
+                                               N, maxiter=maxiter, maxfun=_MAXFUN,
+                                               chunk=chunk)
+
+    def col(name, dtype):
+        return np.array([getattr(q, name) for q in res], dtype=dtype).reshape(B, S)
+
+    Xf = np.array([q.x[:] for q in res], dtype=np.float64).reshape(B, S, N_PARAMS)
+
+    def model_prices_of(params, markets):
+        rec = np.zeros((params.shape[0], _native.PARAM_STRIDE))
+        rec[:, :13] = params
+        rec[:, 13] = sp[markets]
+        rec[:, 14] = r[markets]
+        return surf.price(rec, N)                      # every winner in one launch
+
+    return summarize(mkt, sp, r, Kabs, T, flags, Xf, col("fun", np.float64),
+                     col("nit", np.int64), col("nfev", np.int64), col("task", np.int64),
+                     col("warnflag", np.int64), col("best_loss", np.float64),
+                     col("n_calls", np.int64), col("t_done", np.float64), model_prices_of,
+                     enqueued)
