@@ -455,6 +455,47 @@ int dh_calibrate_lbfgs_batch(dh_ctx* ctx, const dh_surface* s, const double* mkt
                              const int32_t* market_of, int S, int N, double L,
                              const dh_lb_options* opt, dh_lb_result* out, int32_t* n_launches);
 
+/* ---- many markets on one grid, in implied-vol space (csrc/dh_iv_loss_rows.h) -- */
+/* Replaces the loop DoubleHestonJumpCalibrator(spot_b, r_b, options_b, objective="iv").calibrate(
+ * driver="scipy") over the markets: the vol-space objective of dh_surface_loss_iv, against a
+ * market row per param set as dh_surface_loss_rows has it.
+ * The reduction stage alone, over prices already on the device: d_prices [S][M] as
+ * dh_surface_price_dev writes them, d_params the records they were priced under (S0, r, q of set
+ * s from its record, so each set inverts with its own market's spot), d_mkt_iv [B][M] market vols
+ * and d_wgt [B][M] weights in the caller's option order, d_row [S] the market row of each set (in
+ * [0, B); the caller's promise).  Per set s, with b = d_row[s], by dh_surface_iv_sse_dev's rules
+ * (bad prices, the clamp at the lower bound, iv as used):
+ *   sse[s]   = sum of w[b][m] (v - mkt_iv[b][m])^2 over options with w[b][m] > 0 that are not bad
+ *   n_bad[s] = #{m : w[b][m] > 0 and option m is bad}
+ *   iv[s*M + m] = v as used (d_iv NULL to skip)
+ * One wave per set: lane l adds the surface's sorted options l, l + 64, ... in order from 0.0,
+ * then the xor butterfly over the 64 lanes (offsets 1, 2, 4, 8, 16, 32); nothing is contracted.
+ * For M <= 64 these are dh_surface_iv_sse_dev's bits for the same vols and weights.  sse[s]
+ * depends on nothing but set s's record, prices and market row.  Enqueues on `stream` (NULL = the
+ * context's); no synchronisation, no allocation.                                                */
+int dh_surface_iv_sse_rows_dev(dh_ctx* ctx, const dh_surface* s, const double* d_params,
+                               const double* d_prices, const double* d_mkt_iv, const double* d_wgt,
+                               const int32_t* d_row, int S, double* d_sse, int32_t* d_n_bad,
+                               double* d_iv, void* stream);
+/* The host-pointer form, synchronous: params [S][16] are priced as dh_surface_price prices them,
+ * then reduced against mkt_iv [B][M] and wgt [B][M] (NULL: every weight 1) by row [S]; sse [S],
+ * n_bad [S] and the optional prices [S][M], iv [S][M] out.  DH_E_ARG for a row outside [0, B). */
+int dh_surface_loss_iv_rows(dh_ctx* ctx, const dh_surface* s, const double* params,
+                            const double* mkt_iv, const double* wgt, const int32_t* row, int S,
+                            int B, int N, double L, double* sse, int32_t* n_bad, double* prices,
+                            double* iv);
+/* dh_calibrate_lbfgs_batch in vol space: start i fits the vols mkt_iv[market_of[i]][M] under the
+ * weights wgt[market_of[i]][M] (NULL: every weight 1), loss = n_bad ? 1e10 : sse / wsum + Feller,
+ * wsum the market's weight sum (formed on the host: option order, sequential, from 0.0).  Every
+ * iteration is three launches: price, the reduction above, step.  Everything else is
+ * dh_calibrate_lbfgs_batch's, its DH_E_ARG cases included; DH_E_ARG also for a weight that is
+ * negative or not finite, a market whose weights sum to 0, and a market vol that is negative or
+ * not finite at a positive weight (the message names the market and the option).               */
+int dh_calibrate_lbfgs_batch_iv(dh_ctx* ctx, const dh_surface* s, const double* mkt_iv,
+                                const double* wgt, const double* spot, const double* rate, int B,
+                                const double* x0, const int32_t* market_of, int S, int N, double L,
+                                const dh_lb_options* opt, dh_lb_result* out, int32_t* n_launches);
+
 /* ---- building blocks (exposed for API parity with the reference's public methods) -------- */
 /* phi(u_j; tau) for one param set: DoubleHeston.characteristic_function (double_heston.py:48-97) */
 int dh_cf(dh_ctx* ctx, const double* params, const double* u, int n, double tau, double* re,

@@ -2891,6 +2891,8 @@ struct dh_ctx {
     DevBuf rows_mkt, rows_row;         // market rows / row of each set (dh_loss_rows.h)
     // dh_calibrate_lbfgs_batch: the requests' prices, and each start's spot, rate and market
     DevBuf lb_prices, lb_spot, lb_rate, lb_mof;
+    // the vol-space rows (dh_iv_loss_rows.h): weight rows [B][M], each start's weight sum
+    DevBuf rows_wgt, lb_div;
 };
 
 struct dh_surface {
@@ -3445,7 +3447,8 @@ int dh_ctx_destroy(dh_ctx* ctx) {
                       &ctx->lb_sse, &ctx->lb_bad, &ctx->lb_live, &ctx->lb_done, &ctx->lb_x0,
                       &ctx->lb_trace, &ctx->lb_trace_n, &ctx->iv, &ctx->iv_part_sse,
                       &ctx->iv_part_bad, &ctx->rows_mkt, &ctx->rows_row, &ctx->lb_prices,
-                      &ctx->lb_spot, &ctx->lb_rate, &ctx->lb_mof})
+                      &ctx->lb_spot, &ctx->lb_rate, &ctx->lb_mof, &ctx->rows_wgt,
+                      &ctx->lb_div})
         b->release();
     ctx->h_params.release();
     ctx->h_loss.release();
@@ -4207,6 +4210,9 @@ struct LbArgs {
     const double* rate_of;     // [S]
     const int* market_of;      // [S]
     int* row;                  // [n_live * 14]
+    // dh_calibrate_lbfgs_batch_iv only (lb_step_kernel<., true, true>), appended again: each
+    // start's loss divisor, its market's weight sum (dh_iv_loss_rows.h)
+    const double* div_of;      // [S]
 };
 static_assert(std::is_standard_layout<LbArgs>::value, "lb_live_inline reads LbArgs by offset");
 
@@ -4342,8 +4348,10 @@ __device__ __forceinline__ void lb_tile_tree(const double* ps, int nt, double& s
 // component i), run the L-BFGS-B state machine until it needs a new point, emit that request,
 // store the state.  kB: dh_calibrate_lbfgs_batch's build -- the emitted records carry the start's
 // own spot and rate (lb_emit<true>) and the trace's first spare double the start's market; the
-// two kB = false builds are dh_calibrate_lbfgs's, unchanged.
-template <bool kPre, bool kB = false>
+// two kB = false builds are dh_calibrate_lbfgs's, unchanged.  kIv (with kB):
+// dh_calibrate_lbfgs_batch_iv's builds -- the request's sse is dh_iv_loss_rows.h's and the loss
+// divides it by the start's weight sum (div_of) where the price objective divides by M.
+template <bool kPre, bool kB = false, bool kIv = false>
 __global__ __launch_bounds__(64) void lb_step_kernel(
     LbSlot* __restrict__ h_states, const double* __restrict__ h_part, int h_ntiles, int h_mode,
     int h_part_mode, int h_l0, int h_l1, int h_l2, int h_l3, LbArgs A_) {
@@ -4429,7 +4437,12 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
     if (h_mode == 1) {
         t_load = lb_clock();
         double f = __builtin_huge_val();
-        if ((lane & 15) < dhlb::kPts) f = req_bad > 0 ? kInvalidLoss : req_sse / (double)A.M + pen.v;
+        if constexpr (kIv) {
+            if ((lane & 15) < dhlb::kPts)
+                f = req_bad > 0 ? kInvalidLoss : req_sse / A.div_of[sidx] + pen.v;
+        } else {
+            if ((lane & 15) < dhlb::kPts) f = req_bad > 0 ? kInvalidLoss : req_sse / (double)A.M + pen.v;
+        }
         if (lane < dhlb::kLanes) fl[lane] = f;
         __syncthreads();
         const double lo = row_min((f == f && f != kInvalidLoss) ? f : __builtin_huge_val());
@@ -4497,7 +4510,23 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
 #endif
 }
 
-int launch_lb_step(hipStream_t st, const LbArgs& A, int n_live, bool batch = false) {
+int launch_lb_step(hipStream_t st, const LbArgs& A, int n_live, bool batch = false,
+                   bool iv = false) {
+    if (batch && iv) {
+        if (A.n_inline && n_live <= kLbPre) {
+            int l[kLbPre] = {0, 0, 0, 0};
+            for (int i = 0; i < n_live; ++i) l[i] = A.live_inline[i];
+            hipLaunchKernelGGL((lb_step_kernel<true, true, true>), dim3((unsigned)n_live),
+                               dim3(64), 0, st, A.states, A.part_sse, A.n_tiles, A.mode,
+                               A.part_mode, l[0], l[1], l[2], l[3], A);
+        } else {
+            hipLaunchKernelGGL((lb_step_kernel<false, true, true>), dim3((unsigned)n_live),
+                               dim3(64), 0, st, A.states, A.part_sse, A.n_tiles, A.mode,
+                               A.part_mode, 0, 0, 0, 0, A);
+        }
+        HIP_TRY(hipGetLastError());
+        return DH_OK;
+    }
     if (batch) {
         if (A.n_inline && n_live <= kLbPre) {
             int l[kLbPre] = {0, 0, 0, 0};
@@ -4534,14 +4563,25 @@ struct LbBatch {
     const double* rate;
     int B;
     const int32_t* market_of;
+    // dh_calibrate_lbfgs_batch_iv: mkt holds the market vols; the weight rows [B][M] and each
+    // market's weight sum [B] (null: the price objective)
+    const double* iv_wgt = nullptr;
+    const double* iv_wsum = nullptr;
 };
 
 }  // namespace
 
 #include "dh_loss_rows.h"
 
+// dh_iv_loss_rows.h's launch (defined after dh_iv.h, below)
+static int iv_rows_launch(dh_ctx* ctx, const dh_surface* s, const double* d_params,
+                          const double* d_prices, const double* d_mkt_iv, const double* d_wgt,
+                          const int32_t* d_row, int S, double* d_sse, int32_t* d_n_bad,
+                          double* d_iv, void* stream, const int* live_count);
+
 // dh_calibrate_lbfgs (bt null: one market, the surface's, through the fused loss launches) and
 // dh_calibrate_lbfgs_batch (bt: a market per start, through price + dh_loss_rows.h's reduction)
+// and dh_calibrate_lbfgs_batch_iv (bt with weights: through price + dh_iv_loss_rows.h's)
 static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, double S0, double r,
                   int N, double L, const dh_lb_options* opt, dh_lb_result* out,
                   int32_t* n_launches, const LbBatch* bt) {
@@ -4613,7 +4653,17 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
                                hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(ctx->lb_mof.ptr, bt->market_of, (size_t)S * 4, hipMemcpyHostToDevice,
                                st));
-        HIP_TRY(hipStreamSynchronize(st));            // `sr` is pageable and leaves scope
+        std::vector<double> dv;
+        if (bt->iv_wgt) {                             // each start's weight sum, gathered as well
+            HIP_TRY(ctx->rows_wgt.reserve(mb));
+            HIP_TRY(ctx->lb_div.reserve((size_t)S * 8));
+            dv.resize(S);
+            for (int i = 0; i < S; ++i) dv[i] = bt->iv_wsum[bt->market_of[i]];
+            HIP_TRY(hipMemcpyAsync(ctx->rows_wgt.ptr, bt->iv_wgt, mb, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->lb_div.ptr, dv.data(), (size_t)S * 8,
+                                   hipMemcpyHostToDevice, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));            // `sr`, `dv` are pageable and leave scope
     }
     if (!ctx->lb_ev[0]) {
         for (hipEvent_t& e : ctx->lb_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -4657,12 +4707,14 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
     A.market_of = bt ? (const int*)ctx->lb_mof.ptr : nullptr;
     A.row = bt ? (int*)ctx->rows_row.ptr : nullptr;
     const bool batch = bt != nullptr;
+    const bool iv = batch && bt->iv_wgt != nullptr;
+    A.div_of = iv ? (const double*)ctx->lb_div.ptr : nullptr;
     auto set_inline = [&](const int* lst, int n) {
         A.n_inline = n <= kLbInline ? 1 : 0;
         for (int i = 0; i < kLbInline; ++i) A.live_inline[i] = i < n && A.n_inline ? lst[i] : 0;
     };
     set_inline(h_live[0], S);
-    rc = launch_lb_step(st, A, S, batch);
+    rc = launch_lb_step(st, A, S, batch, iv);
     if (rc) return rc;
 
     // Chunks of `chunk` iterations (loss launch(es) + step launch) are enqueued two ahead of the
@@ -4692,12 +4744,19 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
                 e = surface_price_launch_lb(ctx, s, A.rec, (int64_t)n_live * dhlb::kPts, N, L,
                                             (double*)ctx->lb_prices.ptr, st, A.live_count);
                 if (e) return e;
-                e = loss_rows_launch(ctx, s, (const double*)ctx->lb_prices.ptr,
-                                     (const double*)ctx->rows_mkt.ptr, (const int32_t*)A.row,
-                                     n_live * dhlb::kPts, (double*)A.sse, (int32_t*)A.bad, st,
-                                     A.live_count);
+                if (iv)                                // the vol-space reduction: rows_mkt holds vols
+                    e = iv_rows_launch(ctx, s, A.rec, (const double*)ctx->lb_prices.ptr,
+                                       (const double*)ctx->rows_mkt.ptr,
+                                       (const double*)ctx->rows_wgt.ptr, (const int32_t*)A.row,
+                                       n_live * dhlb::kPts, (double*)A.sse, (int32_t*)A.bad,
+                                       nullptr, st, A.live_count);
+                else
+                    e = loss_rows_launch(ctx, s, (const double*)ctx->lb_prices.ptr,
+                                         (const double*)ctx->rows_mkt.ptr, (const int32_t*)A.row,
+                                         n_live * dhlb::kPts, (double*)A.sse, (int32_t*)A.bad, st,
+                                         A.live_count);
                 if (e) return e;
-                e = launch_lb_step(st, A, n_live, true);     // part_mode 0: reads sse / bad
+                e = launch_lb_step(st, A, n_live, true, iv);   // part_mode 0: reads sse / bad
                 if (e) return e;
                 ++launches;
                 continue;
@@ -4754,7 +4813,7 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
                                        hipMemcpyHostToDevice, st));
             }
             A.mode = 2;
-            rc = launch_lb_step(st, A, n_live, batch);
+            rc = launch_lb_step(st, A, n_live, batch, iv);
             if (rc) return rc;
         }
         rc = enqueue_chunk(k + 2);
@@ -5316,4 +5375,5 @@ extern "C" int dh_allgather_best(dh_comm* c, const double* rec, int rows, int wi
 #include "dh_gen_device.h"
 #include "dh_iv.h"
 #include "dh_iv_loss.h"
+#include "dh_iv_loss_rows.h"
 #include "dh_math_probe.h"

@@ -135,6 +135,13 @@ SIGNATURES = {
     "dh_calibrate_lbfgs_batch": (C.c_int, [_vp, _vp, _dp, _dp, _dp, C.c_int, _dp, _i32p, C.c_int,
                                            C.c_int, C.c_double, C.POINTER(LbOptions),
                                            C.POINTER(LbResult), _i32p]),
+    "dh_surface_iv_sse_rows_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp,
+                                             _vp, _vp]),
+    "dh_surface_loss_iv_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                          C.c_double, _vp, _vp, _vp, _vp]),
+    "dh_calibrate_lbfgs_batch_iv": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, C.c_int, _dp, _i32p,
+                                              C.c_int, C.c_int, C.c_double, C.POINTER(LbOptions),
+                                              C.POINTER(LbResult), _i32p]),
     "dh_cf":(C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, _dp, _dp]),
     "dh_cf_complex": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp]),
     "dh_trunc_range": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int64, C.c_double, _dp, _dp]),
@@ -480,6 +487,41 @@ def lb_batch_args(M, mkt, spots, rates, x0s, market_of):
     return mkt, spots, rates, x0s, np.ascontiguousarray(mof, dtype=np.int32)
 
 
+def iv_rows(M, mkt_iv, weights):
+    """Market vols [B, M] and weights ([B, M], [M] for every market, or None for all 1) of the
+    vol-space rows as contiguous arrays, checked as dh_calibrate_lbfgs_batch_iv checks them:
+    weights finite and >= 0 with a positive sum per market, vols finite and >= 0 wherever the
+    weight is positive (anything where it is 0).  -> (mkt_iv [B, M], weights [B, M]), or
+    ValueError naming the (market, option) pairs."""
+    iv = _f64(mkt_iv)
+    if iv.ndim != 2 or iv.shape[1] != M:
+        raise ValueError(f"market vols must be [B, {M}], got {iv.shape}")
+    B = iv.shape[0]
+    if weights is None:
+        w = np.ones((B, M))
+    else:
+        w = _f64(weights)
+        if w.shape == (M,):
+            w = np.ascontiguousarray(np.broadcast_to(w, (B, M)))
+        elif w.shape != (B, M):
+            raise ValueError(f"vol weights must be [{M}] or [{B}, {M}], got {w.shape}")
+    wrong = np.argwhere(~(np.isfinite(w) & (w >= 0)))
+    if wrong.size:
+        raise ValueError("vol weights must be finite and non-negative; (market, option) "
+                         f"{wrong[:8].tolist()}")
+    if M:
+        zero = np.flatnonzero(~(w.sum(axis=1) > 0))
+        if zero.size:
+            raise ValueError(f"the vol weights of market(s) {zero[:8].tolist()} sum to zero")
+    wrong = np.argwhere((w > 0) & ~(np.isfinite(iv) & (iv >= 0)))
+    if wrong.size:
+        raise ValueError(
+            f"no implied vol for (market, option) {wrong[:8].tolist()}"
+            f"{' ...' if len(wrong) > 8 else ''} (price outside its no-arbitrage bounds, or a "
+            "non-finite vol); give them iv_weights of 0")
+    return iv, w
+
+
 class Surface:
     """An option set resident in HBM, grouped by maturity into <=256-option tiles (dh_surface)."""
 
@@ -628,6 +670,71 @@ class Surface:
                                                    _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p),
                                                    S, int(N), float(L), C.byref(opt), res,
                                                    C.byref(nl)))
+        return list(res)[:S], nl.value
+
+    def loss_terms_iv_rows(self, params, mkt_iv, row, N=128, L=10.0, weights=None,
+                           want_prices=False, want_iv=False):
+        """dh_surface_loss_iv_rows -> (sse[S], n_bad[S][, prices[S,M]][, iv[S,M]]): the weighted
+        squared vol errors of every param row (inverted under its own spot, rate and q) against
+        row mkt_iv[row[s]] of the market vols mkt_iv [B, M] under weights [B, M] (None: all 1),
+        and the count of weighted options without a vol; iv holds the vols as used."""
+        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        S = params.shape[0]
+        mkt_iv = (_f64(mkt_iv).reshape(-1, self.M) if self.M
+                  else _f64(mkt_iv).reshape(len(mkt_iv), 0))
+        B = mkt_iv.shape[0]
+        w = None
+        if weights is not None:
+            w = _f64(weights)
+            if w.shape != mkt_iv.shape:
+                raise ValueError(f"weights must be {mkt_iv.shape}, got {w.shape}")
+        row = np.ascontiguousarray(row, dtype=np.int32).reshape(-1)
+        if row.size != S:
+            raise ValueError("params and row differ in length")
+        sse = np.empty(S)
+        bad = np.empty(S, dtype=np.int32)
+        prices = np.empty((S, self.M)) if want_prices else None
+        iv = np.empty((S, self.M)) if want_iv else None
+        with self.ctx._lock:
+            _check(load().dh_surface_loss_iv_rows(
+                self.ctx.handle, self._h, params.ctypes.data, mkt_iv.ctypes.data,
+                None if w is None else w.ctypes.data, row.ctypes.data, S, B, int(N), float(L),
+                sse.ctypes.data, bad.ctypes.data,
+                None if prices is None else prices.ctypes.data,
+                None if iv is None else iv.ctypes.data))
+        return (sse, bad) + ((prices,) if want_prices else ()) + ((iv,) if want_iv else ())
+
+    def iv_sse_rows_dev(self, d_params: int, d_prices: int, d_mkt_iv: int, d_wgt: int, d_row: int,
+                        S: int, d_sse: int, d_bad: int, d_iv: int = 0, stream: int = 0):
+        """dh_surface_iv_sse_rows_dev: the per-row vol-space reduction over [S, M] prices on the
+        device."""
+        _check(load().dh_surface_iv_sse_rows_dev(self.ctx.handle, self._h, _vp(d_params),
+                                                 _vp(d_prices), _vp(d_mkt_iv), _vp(d_wgt),
+                                                 _vp(d_row), int(S), _vp(d_sse), _vp(d_bad),
+                                                 _vp(d_iv) if d_iv else None,
+                                                 _vp(stream) if stream else None))
+
+    def calibrate_lbfgs_batch_iv(self, mkt_iv, weights, spots, rates, x0s, market_of, N=128,
+                                 L=10.0, *, maxiter=300, maxfun=15000, maxls=20, ftol=1e-9,
+                                 gtol=1e-6, chunk=8, ctx=None):
+        """calibrate_lbfgs_batch in implied-vol space (dh_calibrate_lbfgs_batch_iv): row i of x0s
+        [S, 13] fits the vols mkt_iv[b] of market b = market_of[i] under weights[b] (weights
+        [B, M], [M] or None for all 1), spot spots[b], rate rates[b].
+        -> (list of LbResult, number of iterations enqueued)."""
+        ctx = ctx or self.ctx
+        mkt_iv, spots, rates, x0s, mof = lb_batch_args(self.M, mkt_iv, spots, rates, x0s,
+                                                       market_of)
+        mkt_iv, w = iv_rows(self.M, mkt_iv, weights)
+        B, S = mkt_iv.shape[0], x0s.shape[0]
+        opt = LbOptions(int(maxiter), int(maxfun), int(maxls), int(chunk), float(ftol),
+                        float(gtol))
+        res = (LbResult * max(S, 1))()
+        nl = C.c_int32(0)
+        with ctx._lock:
+            _check(load().dh_calibrate_lbfgs_batch_iv(ctx.handle, self._h, _ptr(mkt_iv), _ptr(w),
+                                                      _ptr(spots), _ptr(rates), B, _ptr(x0s),
+                                                      _ptr(mof, _i32p), S, int(N), float(L),
+                                                      C.byref(opt), res, C.byref(nl)))
         return list(res)[:S], nl.value
 
     def fg(self, X0, S0, r, N=128, L=10.0, model=None):

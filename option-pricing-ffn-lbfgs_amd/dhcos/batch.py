@@ -8,6 +8,10 @@ under moving spots -- run every start of every market through the same launches
 start's pending request in one launch, reduces each against its own market's prices and advances
 every start's L-BFGS-B state.  A start's trajectory depends on its own x0 and market alone, so a
 market's result does not depend on what else is in the batch.
+
+``objective="iv"`` fits implied vols instead of relative prices (dh_calibrate_lbfgs_batch_iv,
+DESIGN.md 3.13): the loss of a market is sum_m w_m (iv_model,m - iv_mkt,m)^2 / sum(w) + Feller,
+with every model price inverted on the device under its own market's spot and rate.
 """
 from __future__ import annotations
 
@@ -20,7 +24,9 @@ from . import _native
 from .calibrator import (_MAXFUN, N_PARAMS, PARAM_NAMES, CalibrationResult,
                          DoubleHestonJumpCalibrator, x_to_model)
 from .generator import MATURITIES, STRIKES_PCT, grid_surface
-from .pricer import resolve_call
+from .pricer import implied_vol, resolve_call
+
+OBJECTIVES = ("price", "iv")
 
 FAILED_MESSAGE = "All optimization starts failed"      # lbfgs_calibrator.py:318-333
 
@@ -74,6 +80,11 @@ class BatchCalibrationResult:
     n_calls: np.ndarray          # [B, S]
     start_x: np.ndarray          # [B, S, 13]
     iterations_enqueued: int = 0
+    # objective="iv": final_loss, fun and best_loss are vol-space losses
+    objective: str = "price"
+    market_ivs: np.ndarray = None    # [B, M] the vols fitted (None under "price")
+    iv_weights: np.ndarray = None    # [B, M]
+    model_ivs: np.ndarray = None     # [B, M] the winners' vols, NaN where a price has none
 
     def message(self, b: int) -> str:
         return task_message(self.task[b]) if self.best_start[b] >= 0 else FAILED_MESSAGE
@@ -143,6 +154,37 @@ def check_markets(market_prices, spots, risk_free, M):
     return mkt, sp, np.ascontiguousarray(r)
 
 
+def check_objective(objective):
+    if objective not in OBJECTIVES:
+        raise ValueError(f"objective must be 'price' or 'iv', not {objective!r}")
+    return objective
+
+
+def check_iv_market(market_ivs, iv_weights, B, M):
+    """-> (market_ivs [B, M], iv_weights [B, M]) as float64, or ValueError: iv_weights is [M]
+    (every market's) or [B, M], default 1, finite, >= 0 and not all 0 in any market; a market vol
+    must be finite and >= 0 wherever its weight is positive (the message names the markets and
+    options)."""
+    iv = np.ascontiguousarray(market_ivs, dtype=np.float64)
+    if iv.shape != (B, M):
+        raise ValueError(f"market_ivs must be [{B}, {M}], got {iv.shape}")
+    if iv_weights is not None:
+        w = np.asarray(iv_weights, dtype=np.float64)
+        if w.shape not in ((M,), (B, M)):
+            raise ValueError(f"iv_weights must be [{M}] or [{B}, {M}], got {w.shape}")
+        iv_weights = w
+    return _native.iv_rows(M, iv, iv_weights)
+
+
+def invert_markets(mkt, sp, r, Kabs, T, flags, device=None):
+    """The market vols [B, M] of market prices [B, M]: one dh_implied_vol call at each market's
+    spot and rate and q = 0 (what DoubleHestonJumpCalibrator(objective="iv") forms for one
+    market); NaN where a price has no vol."""
+    return np.ascontiguousarray(
+        implied_vol(mkt, sp[:, None], Kabs, T[None, :], r[:, None], 0.0, flags[None, :],
+                    device=device), dtype=np.float64).reshape(mkt.shape)
+
+
 def _options(b, mkt, sp, Kabs, T, flags):
     return [{"strike": Kabs[b, j], "maturity": T[j], "price": mkt[b, j],
              "option_type": "call" if flags[j] else "put"} for j in range(T.size)]
@@ -208,11 +250,14 @@ def _surface(ctx, K, T, flags, mode, strikes_pct, maturities):
 
 
 def summarize(mkt, sp, r, Kabs, T, flags, X, fun, nit, nfev, task, status, best_loss, n_calls,
-              t_done, model_prices_of, enqueued=0) -> BatchCalibrationResult:
+              t_done, model_prices_of, enqueued=0, *, objective="price", market_ivs=None,
+              iv_weights=None) -> BatchCalibrationResult:
     """Per-market rows from per-start results [B, S]: the winner of each market
     (pick_winners), re-priced by model_prices_of(params [W, 13], markets [W]) -> [W, M] in one
     call; a market without a winner gets the reference's failure row (zeros, inf, success
-    False)."""
+    False).  objective="iv": model_prices_of returns (prices [W, M], vols [W, M]) of that one
+    call, and the result carries the market vols, the weights and the winners' vols."""
+    check_objective(objective)
     B, M = mkt.shape
     best = pick_winners(fun)
     won = np.flatnonzero(best >= 0)
@@ -224,6 +269,7 @@ def summarize(mkt, sp, r, Kabs, T, flags, X, fun, nit, nfev, task, status, best_
     ok = np.zeros(B, dtype=bool)
     wtask = np.zeros(B, dtype=np.int64)
     model = np.zeros((B, M))
+    model_iv = np.zeros((B, M)) if objective == "iv" else None
     ctime = np.zeros(B)
     if won.size:
         x[won] = X[won, bw]
@@ -233,18 +279,23 @@ def summarize(mkt, sp, r, Kabs, T, flags, X, fun, nit, nfev, task, status, best_
         ok[won] = status[won, bw] == 0
         wtask[won] = task[won, bw]
         ctime[won] = t_done[won, bw]
-        model[won] = model_prices_of(params[won], won)
+        if objective == "iv":
+            model[won], model_iv[won] = model_prices_of(params[won], won)
+        else:
+            model[won] = model_prices_of(params[won], won)
     return BatchCalibrationResult(
         spots=sp, risk_free=r, market_prices=mkt, strikes=Kabs, maturities=T, is_call=flags,
         parameters=params, x=x, final_loss=final, iterations=iters, success=ok, task=wtask,
         best_start=best, model_prices=model, calibration_time=ctime, fun=fun, nit=nit, nfev=nfev,
         start_task=task, status=status, best_loss=best_loss, n_calls=n_calls, start_x=X,
-        iterations_enqueued=enqueued)
+        iterations_enqueued=enqueued, objective=objective, market_ivs=market_ivs,
+        iv_weights=iv_weights, model_ivs=model_iv)
 
 
 def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
                     maturities=MATURITIES, strikes=None, is_call=True, x0s=None, multi_start=3,
-                    maxiter=300, N=128, device=None, chunk=8) -> BatchCalibrationResult:
+                    maxiter=300, N=128, device=None, chunk=8, objective="price",
+                    market_ivs=None, iv_weights=None) -> BatchCalibrationResult:
     """Calibrate B markets that share one option grid, all starts of all markets together in the
     device-resident L-BFGS-B.
 
@@ -253,12 +304,34 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
     each market's spot), or strikes x maturities (absolute, the same for every market).
     x0s: [B, S, 13] unconstrained start points, [B][S] dicts of the 13 model parameters, or None
     for each market's start_points(multi_start) (the global RNG is consumed as a loop of
-    calibrate() calls over the markets would consume it)."""
+    calibrate() calls over the markets would consume it).
+
+    objective="price" (the default) fits relative price errors, the reference's loss.
+    objective="iv" fits Black-Scholes vols: market_ivs [B, M] (default: the device inversion of
+    market_prices at each market's spot and rate and q = 0, one call) under iv_weights [M] or
+    [B, M] (default 1; 0 drops an option), loss = sum w (iv_model - iv_mkt)^2 / sum(w) + Feller.
+    A market without a vol at a positive weight raises ValueError naming the markets and options,
+    before any start is drawn.  final_loss and fun are then vol-space losses and the result's
+    model_ivs holds the winners' vols.  The generator's vols fit as they are:
+
+        g = generate_synthetic_calibrations(n, None, as_arrays=True, implied_vols=True)
+        calibrate_batch(g["market_prices"], g["spot"], g["risk_free"], objective="iv",
+                        market_ivs=g["market_iv"], x0s=...)
+
+    One market in vol space on the device is this call with B = 1."""
+    check_objective(objective)
+    if objective == "price" and (market_ivs is not None or iv_weights is not None):
+        raise ValueError("market_ivs and iv_weights belong to objective='iv'")
     K, T, flags, mode = _grid(strikes_pct, maturities, strikes, is_call)
     mkt, sp, r = check_markets(market_prices, spots, risk_free, K.size)
     B = mkt.shape[0]
     Kabs = (K[None, :] * sp[:, None] / 100.0 if mode == _native.STRIKE_PCT_SPOT
             else np.broadcast_to(K, (B, K.size)).copy())
+    ivs = wts = None
+    if objective == "iv":                               # before any RNG draw
+        if market_ivs is None:
+            market_ivs = invert_markets(mkt, sp, r, Kabs, T, flags, device)
+        ivs, wts = check_iv_market(market_ivs, iv_weights, B, K.size)
     if x0s is None:
         if int(multi_start) < 0:
             raise ValueError("multi_start < 0")
@@ -269,9 +342,14 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
     ctx = _native.default_context(device)
     surf = _surface(ctx, K, T, flags, mode, strikes_pct, maturities)
     market_of = np.repeat(np.arange(B, dtype=np.int32), S)
-    res, enqueued = surf.calibrate_lbfgs_batch(mkt, sp, r, X.reshape(B * S, N_PARAMS), market_of,
-                                               N, maxiter=maxiter, maxfun=_MAXFUN,
-                                               chunk=chunk)
+    if objective == "iv":
+        res, enqueued = surf.calibrate_lbfgs_batch_iv(ivs, wts, sp, r, X.reshape(B * S, N_PARAMS),
+                                                      market_of, N, maxiter=maxiter,
+                                                      maxfun=_MAXFUN, chunk=chunk)
+    else:
+        res, enqueued = surf.calibrate_lbfgs_batch(mkt, sp, r, X.reshape(B * S, N_PARAMS),
+                                                   market_of, N, maxiter=maxiter, maxfun=_MAXFUN,
+                                                   chunk=chunk)
 
     def col(name, dtype):
         return np.array([getattr(q, name) for q in res], dtype=dtype).reshape(B, S)
@@ -283,10 +361,13 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
         rec[:, :13] = params
         rec[:, 13] = sp[markets]
         rec[:, 14] = r[markets]
+        if objective == "iv":                          # priced and inverted in one call
+            iv, prices = surf.implied_vol(rec, N, want_prices=True)
+            return prices, iv
         return surf.price(rec, N)                      # every winner in one launch
 
     return summarize(mkt, sp, r, Kabs, T, flags, Xf, col("fun", np.float64),
                      col("nit", np.int64), col("nfev", np.int64), col("task", np.int64),
                      col("warnflag", np.int64), col("best_loss", np.float64),
                      col("n_calls", np.int64), col("t_done", np.float64), model_prices_of,
-                     enqueued)
+                     enqueued, objective=objective, market_ivs=ivs, iv_weights=wts)

@@ -458,7 +458,9 @@ class DoubleHestonJumpCalibrator:
         reference's optimizer, bit for bit).  driver="device": the device-resident L-BFGS-B
         (dh_calibrate_lbfgs: the loss launches and the optimizer steps run back to back on the
         GPU, the host checks for finished starts every few iterations); same algorithm and
-        stopping rules, with the subspace step rounded differently (csrc/dh_lbfgs.h)."""
+        stopping rules, with the subspace step rounded differently (csrc/dh_lbfgs.h).
+        driver="device" is refused with objective="iv": one market in vol space on the device
+        is ``dhcos.calibrate_batch(..., objective="iv")`` with B = 1."""
         start_time = time.time()
         if driver == "device" and self.objective != "price":
             raise ValueError("driver='device' optimises the price objective only; "
@@ -1007,7 +1009,9 @@ def run_starts_device(cal: DoubleHestonJumpCalibrator, x0s, maxiter: int):
     and optimizer steps run on the GPU; returns [(OptimizeResult, t_done)] in start order.
     Markets whose loss is constant (an option type of '' -> 1e10, no options -> NaN) have
     nothing to optimise on the device and take the host driver, which reproduces the
-    reference's result for them."""
+    reference's result for them.  A calibrator with objective="iv" is refused: the vol-space
+    objective runs on the device through ``dhcos.calibrate_batch(..., objective="iv")`` (one
+    market: B = 1)."""
     n = len(x0s)
     if getattr(cal, "objective", "price") != "price":
         raise ValueError("the device-resident L-BFGS-B optimises the price objective only")
