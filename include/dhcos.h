@@ -455,7 +455,7 @@ int dh_calibrate_lbfgs_batch(dh_ctx* ctx, const dh_surface* s, const double* mkt
                              const int32_t* market_of, int S, int N, double L,
                              const dh_lb_options* opt, dh_lb_result* out, int32_t* n_launches);
 
-/* ---- many markets on one grid, in implied-vol space (csrc/dh_iv_loss_rows.h) -- */
+/* ---- many markets on one grid, in implied-vol space (csrc/dh_loss_rows.h) ----- */
 /* Replaces the loop DoubleHestonJumpCalibrator(spot_b, r_b, options_b, objective="iv").calibrate(
  * driver="scipy") over the markets: the vol-space objective of dh_surface_loss_iv, against a
  * market row per param set as dh_surface_loss_rows has it.

@@ -1,7 +1,7 @@
 // dh_lbfgs.h -- L-BFGS-B without bounds as a resumable state machine, for the device-resident
 // calibration driver (dh_calibrate_lbfgs).  One calibration start = one LbCore<V>.  The code is
 // generic in the vector type V: the step kernel instantiates it with one vector component per
-// lane (dh_kernels.hip WaveVec: a 13-vector lives in lanes 0..12 of a wave, dot products are
+// lane (dh_lb_driver.h WaveVec: a 13-vector lives in lanes 0..12 of a wave, dot products are
 // xor butterflies over 16 lanes), the CPU check build (tests/native/lb_host.cpp) with a plain
 // 16-double array whose dot product sums in the same pairwise order -- so both give the same
 // bits.  V provides +, -, * (elementwise), double * V, dot(a, b), amax(a), equal(a, b).  The

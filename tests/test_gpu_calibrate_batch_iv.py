@@ -1,5 +1,5 @@
 """GPU tests of the batched multi-market calibration in implied-vol space
-(csrc/dh_iv_loss_rows.h: dh_surface_iv_sse_rows_dev, dh_surface_loss_iv_rows,
+(csrc/dh_loss_rows.h: dh_surface_iv_sse_rows_dev, dh_surface_loss_iv_rows,
 dh_calibrate_lbfgs_batch_iv; dhcos.calibrate_batch(objective="iv")).  DESIGN.md 3.13.
 
 Markets: those of test_gpu_calibrate_batch.py -- generate_synthetic_calibrations(35,
@@ -119,7 +119,7 @@ def same_bits(a, b):
 # ---- 1. the reduction alone ------------------------------------------------------------------
 
 def iv_rows_reference(iv, mkt_iv, w, row, T):
-    """dh_iv_loss_rows.h's documented order, restated on the vols as used: the surface sorts its
+    """dh_loss_rows.h's documented vol order, restated on the vols as used: the surface sorts its
     options by maturity (stable), lane l takes sorted options l, l + 64, ... -> (sse, n_bad)."""
     S, M = iv.shape
     perm = np.argsort(T, kind="stable")                  # sorted place -> caller's place
