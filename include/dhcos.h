@@ -538,6 +538,55 @@ int dh_allgather_best(dh_comm* comm, const double* rec, int rows, int width, int
 int dh_best_start(const double* all, int64_t rows, int width, int col_start, int col_fun,
                   int* best);
 
+/* ---- Monte Carlo path pricer (csrc/dh_mc.h) --------------------------------- */
+/* Replaces nothing in the reference (it prices European vanillas by COS only): it is where the
+ * calibrated parameters go to price what vanillas cannot, and the one check of the COS prices
+ * that does not pass through the characteristic function.  The model's SDE (q = 0) is simulated
+ * on the uniform grid dt = 1 / steps_per_year, one path per GPU lane: Andersen's QE scheme for
+ * each variance factor, central weights for the log-spot, Poisson jumps by inversion, the running
+ * maximum / minimum / sum of S over the step dates 1..n (discrete monitoring; the start value is
+ * not a date).  Path i's random numbers are Philox4x32-10 blocks keyed by `seed` and counted by
+ * (i, step), so they depend on (seed, i, step) only, and all P parameter sets of a call see the
+ * same draws (common random numbers).  Results are a function of (params, options, n_paths,
+ * steps_per_year, seed) alone: no atomics, every sum in a fixed order.                          */
+enum { DH_MC_EUROPEAN = 0, DH_MC_ASIAN = 1, DH_MC_UP_AND_OUT = 2, DH_MC_DOWN_AND_OUT = 3 };
+#define DH_MC_MAX_OPTIONS 64     /* options of one call (all priced from the same paths) */
+#define DH_MC_POISSON_CAP 16     /* jumps per step at most; lambda / steps_per_year <= 1 */
+typedef struct {
+    int32_t kind;                /* DH_MC_*: european (S_T - K)^+ / (K - S_T)^+; asian: the
+                                    arithmetic mean of S over dates 1..n against K; up_and_out /
+                                    down_and_out: european if the running max stayed < barrier /
+                                    the running min stayed > barrier, else 0 */
+    int32_t is_call;             /* 0 put, else call */
+    double strike;               /* finite, >= 0 */
+    double maturity;             /* years: a whole number n >= 1 of steps (to 1e-9 relative) */
+    double barrier;              /* > 0 for the two barrier kinds; not read otherwise */
+} dh_mc_option;
+/* price[p * n_options + j] = e^{-rT} mean payoff of option j under params[p] (records of
+ * DH_PARAM_STRIDE doubles: 13 model params, S0 at 13, r at 14; q is not read) over paths
+ * 0 .. n_paths - 1, stderr[...] = e^{-rT} sqrt((sum p^2 - (sum p)^2 / n) / (n (n - 1))).  Host
+ * arrays, synchronous.  DH_E_ARG, before any device work, names the argument in dh_last_error():
+ * a parameter that is not finite, v0 < 0, kappa / theta / sigma <= 0, |rho| >= 1, lambda < 0,
+ * lambda / steps_per_year > 1, sigma_j < 0, spot <= 0; n_paths < 2; steps_per_year < 1; P outside
+ * [1, 65535]; n_options outside [1, DH_MC_MAX_OPTIONS]; an unknown kind; a maturity that is not a
+ * whole number of steps; a barrier <= 0 on a barrier option; a strike < 0 or not finite.         */
+int dh_mc_price(dh_ctx* ctx, const double* params, int64_t P, const dh_mc_option* options,
+                int n_options, int64_t n_paths, int steps_per_year, uint64_t seed, double* price,
+                double* stderr_out);
+/* The same over device pointers (d_params [P][16] in, d_price / d_stderr [P][n_options] out;
+ * `options` stays a host array, copied when the call returns): two launches enqueued on `stream`
+ * (hipStream_t; NULL = the context's), no synchronisation, no allocation after warm-up.  The
+ * parameter values are the caller's promise (not readable here); the same bits as dh_mc_price.  */
+int dh_mc_price_dev(dh_ctx* ctx, const double* d_params, int64_t P, const dh_mc_option* options,
+                    int n_options, int64_t n_paths, int steps_per_year, uint64_t seed,
+                    double* d_price, double* d_stderr, void* stream);
+/* Validation export, in the spirit of dh_cf / dh_cos_coeffs: out[((p * n_paths + i) * n_obs + j) *
+ * 6 ..] = S, v1, v2, running max, running min, running sum of path path0 + i under params[p] at
+ * step obs_steps[j] (>= 1, strictly increasing), by the very step function the pricing kernel
+ * runs.  Host arrays, synchronous; n_paths >= 1; at most 2^31 doubles of output per call.       */
+int dh_mc_paths(dh_ctx* ctx, const double* params, int64_t P, int n_obs, const int32_t* obs_steps,
+                int64_t path0, int64_t n_paths, int steps_per_year, uint64_t seed, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2896,6 +2896,9 @@ struct dh_ctx {
     DevBuf lb_prices, lb_spot, lb_rate, lb_mof;
     // the vol-space rows (dh_loss_rows.h): weight rows [B][M], each start's weight sum
     DevBuf rows_wgt, lb_div;
+    // the Monte Carlo pricer (dh_mc.h): staged records, sorted options / observation steps, the
+    // blocks' partial sums, staged outputs
+    DevBuf mc_params, mc_opts, mc_part, mc_out;
 };
 
 struct dh_surface {
@@ -3451,7 +3454,7 @@ int dh_ctx_destroy(dh_ctx* ctx) {
                       &ctx->lb_trace, &ctx->lb_trace_n, &ctx->iv, &ctx->iv_part_sse,
                       &ctx->iv_part_bad, &ctx->rows_mkt, &ctx->rows_row, &ctx->lb_prices,
                       &ctx->lb_spot, &ctx->lb_rate, &ctx->lb_mof, &ctx->rows_wgt,
-                      &ctx->lb_div})
+                      &ctx->lb_div, &ctx->mc_params, &ctx->mc_opts, &ctx->mc_part, &ctx->mc_out})
         b->release();
     ctx->h_params.release();
     ctx->h_loss.release();
@@ -4591,3 +4594,4 @@ extern "C" int dh_allgather_best(dh_comm* c, const double* rec, int rows, int wi
 #include "dh_loss_rows.h"
 #include "dh_lb_driver.h"
 #include "dh_math_probe.h"
+#include "dh_mc.h"

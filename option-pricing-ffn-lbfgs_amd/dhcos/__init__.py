@@ -8,6 +8,7 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
     generate_synthetic_calibrations   src/data/synthetic_generator.py
     implied_vol                       (new: Black-Scholes implied volatility of prices)
     calibrate_batch                   (new: many markets on one option grid, calibrated together)
+    monte_carlo                       (new: path pricing of European, Asian and barrier options)
 
 All pricing arithmetic runs in libdhcos.so (hand-written gfx950 HIP kernels, C-ABI in
 include/dhcos.h); the native library is loaded on first use and there is no CPU fallback.
@@ -19,9 +20,10 @@ from .pricer import DoubleHeston, implied_vol
 from .calibrator import CalibrationResult, DoubleHestonJumpCalibrator
 from .generator import generate_synthetic_calibrations
 from .batch import BatchCalibrationResult, calibrate_batch
+from .montecarlo import MonteCarloResult, monte_carlo
 from ._native import NativeError
 
 __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
            "generate_synthetic_calibrations", "implied_vol", "NativeError", "calibrate_batch",
-           "BatchCalibrationResult"]
+           "BatchCalibrationResult", "monte_carlo", "MonteCarloResult"]
 __version__ = "0.1.0"

@@ -49,8 +49,24 @@ class LbResult(C.Structure):
                 ("task", C.c_int32), ("warnflag", C.c_int32), ("n_calls", C.c_int32),
                 ("pad", C.c_int32)]
 
+class McOption(C.Structure):
+    """dh_mc_option (include/dhcos.h): one option of the Monte Carlo pricer."""
+    _fields_ = [("kind", C.c_int32), ("is_call", C.c_int32), ("strike", C.c_double),
+                ("maturity", C.c_double), ("barrier", C.c_double)]
+
+
+MC_KINDS = {"european": 0, "asian": 1, "up_and_out": 2, "down_and_out": 3}   # DH_MC_*
+MC_MAX_OPTIONS = 64            # DH_MC_MAX_OPTIONS
+MC_POISSON_CAP = 16            # DH_MC_POISSON_CAP
+
 # name -> (restype, argtypes); mirrors include/dhcos.h one to one
 SIGNATURES = {
+    "dh_mc_price": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(McOption), C.c_int, C.c_int64,
+                              C.c_int, C.c_uint64, _vp, _vp]),
+    "dh_mc_price_dev": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(McOption), C.c_int, C.c_int64,
+                                  C.c_int, C.c_uint64, _vp, _vp, _vp]),
+    "dh_mc_paths": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int64, C.c_int,
+                              C.c_uint64, _vp]),
     "dh_version": (C.c_int, []),
     "dh_last_error": (C.c_char_p, []),
     "dh_device_count": (C.c_int, [_i32p]),
@@ -395,6 +411,54 @@ class Context:
             _check(load().dh_implied_vol(self._h, *(c.ctypes.data if n else None for c in cols),
                                          ic.ctypes.data if n else None, n,
                                          out.ctypes.data if n else None))
+        return out
+
+    def mc_price(self, records, options, n_paths, steps_per_year, seed):
+        """dh_mc_price: records [P, 16], options an array of McOption -> (price, stderr), each
+        [P, n_options]."""
+        rec = _f64(records).reshape(-1, PARAM_STRIDE)
+        P, n_opt = rec.shape[0], len(options)
+        price, err = np.empty((P, n_opt)), np.empty((P, n_opt))
+        with self._lock:
+            _check(load().dh_mc_price(self._h, rec.ctypes.data, P, options, n_opt, int(n_paths),
+                                      int(steps_per_year), int(seed), price.ctypes.data,
+                                      err.ctypes.data))
+        return price, err
+
+    def mc_price_dev(self, records, options, n_paths, steps_per_year, seed, stream=None):
+        """dh_mc_price_dev: records a contiguous float64 [P, 16] torch tensor on this context's
+        device -> (price, stderr) tensors [P, n_options], enqueued on ``stream`` (None: the
+        context's own; the null stream cannot be named, as implied_vol_dev) without
+        synchronisation."""
+        import torch
+        if (records.dtype != torch.float64 or not records.is_contiguous() or records.dim() != 2
+                or records.shape[1] != PARAM_STRIDE or not records.is_cuda
+                or records.device.index != self.device):
+            raise ValueError(f"mc_price_dev: a contiguous float64 [P, {PARAM_STRIDE}] tensor on "
+                             f"cuda:{self.device}")
+        P, n_opt = records.shape[0], len(options)
+        out = torch.empty((2, P, n_opt), dtype=torch.float64, device=records.device)
+        st = 0 if stream is None else int(getattr(stream, "cuda_stream", stream))
+        if stream is not None and st == 0:
+            raise ValueError("mc_price_dev: the default (null) stream cannot be named; pass a "
+                             "non-default stream, or None for the context's stream")
+        with self._lock:
+            _check(load().dh_mc_price_dev(self._h, _vp(records.data_ptr()), P, options, n_opt,
+                                          int(n_paths), int(steps_per_year), int(seed),
+                                          _vp(out[0].data_ptr()), _vp(out[1].data_ptr()),
+                                          _vp(st)))
+        return out[0], out[1]
+
+    def mc_paths(self, records, obs_steps, path0, n_paths, steps_per_year, seed):
+        """dh_mc_paths: records [P, 16], obs_steps int32 [n_obs] -> [P, n_paths, n_obs, 6]
+        (S, v1, v2, running max, min, sum)."""
+        rec = _f64(records).reshape(-1, PARAM_STRIDE)
+        obs = np.ascontiguousarray(obs_steps, dtype=np.int32).reshape(-1)
+        out = np.empty((rec.shape[0], int(n_paths), obs.size, 6))
+        with self._lock:
+            _check(load().dh_mc_paths(self._h, rec.ctypes.data, rec.shape[0], obs.size,
+                                      obs.ctypes.data, int(path0), int(n_paths),
+                                      int(steps_per_year), int(seed), out.ctypes.data))
         return out
 
     def implied_vol_dev(self, price, S0, K, T, r, q, is_call, out=None, stream=None):
@@ -1402,4 +1466,5 @@ __all__ = ["gen_draw", "gen_assemble", "gen_dates", "gen_locate", "gen_draw_loca
            "SIGNATURES",
            "Comm", "comm_id", "best_start", "COMM_ID_BYTES", "FgChannel", "pinned",
            "pinned_empty", "host_cache_trim", "gen_device", "gen_log",
-           "math_probe", "MATH_PROBE_FNS", "lb_batch_args"]
+           "math_probe", "MATH_PROBE_FNS", "lb_batch_args",
+           "McOption", "MC_KINDS", "MC_MAX_OPTIONS", "MC_POISSON_CAP"]

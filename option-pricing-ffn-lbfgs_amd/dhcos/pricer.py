@@ -125,6 +125,19 @@ class DoubleHeston:
         return implied_vol(self.pricing(N), self.S0, self.K, self.T, self.r, self.q,
                            self.option_type, device=self.device)
 
+    def monte_carlo(self, n_paths=1 << 20, steps_per_year=64, seed=0):
+        """(price, stderr) of this instance's option by simulating the model's SDE
+        (``dhcos.monte_carlo``; q must be 0, the simulated dynamics carry no dividend yield)."""
+        from .montecarlo import monte_carlo
+        if self.q != 0.0:
+            raise ValueError("monte_carlo: the simulated dynamics have q = 0")
+        res = monte_carlo([getattr(self, f) for f in MODEL_FIELDS], self.S0, self.r,
+                          [{"strike": self.K, "maturity": self.T,
+                            "option_type": self.option_type}],
+                          n_paths=n_paths, steps_per_year=steps_per_year, seed=seed,
+                          device=self.device)
+        return np.float64(res.price[0]), np.float64(res.stderr[0])
+
     # -- batched entry point ----------------------------------------------------------------
     @staticmethod
     def price_batch(params, S0, K, T, r, option_type="C", N=128, q=0.0, L=10.0, device=None):
