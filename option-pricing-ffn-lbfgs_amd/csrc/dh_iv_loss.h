@@ -1,7 +1,7 @@
 // dh_iv_loss.h -- the calibration objective in implied-vol space (dh_surface_set_iv_market,
 // dh_surface_iv_sse_dev, dh_surface_loss_iv_dev, dh_surface_loss_iv), and what the loss stages
 // share: one option's vol term (vol_term), the weight checks (iv_check_weights) and the host
-// scaffolding of a stage (loss_stage, loss_round_trip; dh_loss_rows.h uses them too).  Included by
+// scaffolding of a stage (loss_round_trip, on dh_host.h's loss_stage; dh_loss_rows.h too).  Included by
 // dh_kernels.hip after dh_iv.h.  DESIGN.md 3.11, 3.14.
 //
 // A stage beside the request kernels: it reads the [S][M] prices a pricing request wrote
@@ -175,25 +175,6 @@ struct DrainOnError {
         if (armed) (void)hipStreamSynchronize(st);
     }
 };
-
-// A reduction stage between its argument checks and its kernel: S < 0 is an error and S == 0
-// nothing; a surface with no option gets sse and n_bad zeroed, no launch; otherwise launch(st)
-// runs with the context's device current.
-template <typename Launch>
-int loss_stage(dh_ctx* ctx, const dh_surface* s, int S, double* d_sse, int32_t* d_n_bad,
-               void* stream, Launch&& launch) {
-    if (S < 0) return fail(DH_E_ARG, "S < 0");
-    if (S == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    if (s->M == 0) {
-        HIP_TRY(hipMemsetAsync(d_sse, 0, (size_t)S * 8, st));
-        HIP_TRY(hipMemsetAsync(d_n_bad, 0, (size_t)S * 4, st));
-        return DH_OK;
-    }
-    return launch(st);
-}
 
 // the per-set market rows of the *_rows host entry points (host arrays): mkt [B][M], the row of
 // each set [S], and where `weighted` wgt [B][M] (null: every weight 1)

@@ -1,4 +1,6 @@
-// dh_kernels.hip -- gfx950 kernels and C-ABI of the COS pricing / calibration-objective hot path.
+// dh_kernels.hip -- gfx950 kernels of the COS pricing / calibration-objective hot path, and the
+// library's one translation unit: the host side (launch planner, C ABI) and the features are the
+// headers included at the end.
 //
 // Two kernels per request (DESIGN.md "Kernels"), each with its own small register footprint:
 //
@@ -35,8 +37,6 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <array>
-#include <rccl/rccl.h>   // types only: librccl is resolved at run time (dlopen)
-#include <dlfcn.h>
 
 #include <algorithm>
 #include <chrono>
@@ -44,7 +44,6 @@
 #include <cstdio>
 #include <cstring>
 #include <numeric>
-#include <type_traits>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -2703,1380 +2702,11 @@ __global__ void coeff_kernel(const int32_t* __restrict__ k, int n, double c, dou
     psi[i] = y;
 }
 
-// ----------------------------------------------------------------------------------------------
-// host side
-// ----------------------------------------------------------------------------------------------
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t _e = (expr);                                                            \
-        if (_e != hipSuccess)                                                              \
-            return fail(DH_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));      \
-    } while (0)
-
-struct DevBuf {
-    void* ptr = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-        size_t want = std::max<size_t>(bytes, 4096);
-        hipError_t e = hipMalloc(&ptr, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-    }
-};
-
-// Pinned, device-mapped host memory (grow-only): small request inputs and outputs the kernels
-// read and write directly over PCIe, so a host-API request is one launch and one sync.
-struct HostBuf {
-    void* ptr = nullptr;       // host address
-    void* dptr = nullptr;      // device address of the same bytes
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        release();
-        const size_t want = std::max<size_t>(bytes, 4096);
-        hipError_t e = hipHostMalloc(&ptr, want, hipHostMallocMapped | hipHostMallocCoherent);
-        if (e != hipSuccess) {
-            ptr = nullptr;
-            return e;
-        }
-        e = hipHostGetDevicePointer(&dptr, ptr, 0);
-        if (e != hipSuccess) {
-            release();
-            return e;
-        }
-        cap = want;
-        return hipSuccess;
-    }
-    void release() {
-        if (ptr) (void)hipHostFree(ptr);
-        ptr = dptr = nullptr;
-        cap = 0;
-    }
-};
-
-// Threads per table.  The fused kernel takes one entry per thread up to N = 256 (latency).  The
-// split path's table kernel takes the slot width (64, 128 or 256 threads; 64 = one wave per table
-// defines the canonical order of the k-sums, which the others re-form from LDS) that minimises
-// rounds of resident slots x entries per thread; 64 unless a wider slot saves >= 10% (requests
-// with few tables per slot, e.g. C3: 4,200 tables on 3,072 one-wave slots).
-struct dh_ctx_view {
-    int resident[3] = {0, 0, 0};
-    int resident_gen[3] = {0, 0, 0};   // cos_gen_kernel<16 / 8 / 4> at its N's LDS
-};
-
-int fused_tpt(int N) { return N <= 64 ? 64 : (N <= 128 ? 128 : 256); }
-
-// cos_gen_kernel<TB>: TB tables' (T2, T6) in LDS, <= 32 KB per block (three blocks per CU)
-constexpr int gen_max_n(int TB) { return 2048 / TB; }
-int gen_tb(int N) { return N <= gen_max_n(16) ? 16 : (N <= gen_max_n(8) ? 8 : (N <= gen_max_n(4) ? 4 : 0)); }
-
-int table_tpt(const dh_ctx_view& v, int64_t n_q, int N) {
-    auto cost = [&](int i) {
-        const int tpt = 64 << i;
-        const int64_t slots = (int64_t)std::max(1, v.resident[i]) * (kBlock / tpt);
-        return (double)((n_q + slots - 1) / slots) * (double)((N + tpt - 1) / tpt);
-    };
-    const double c64 = cost(0);
-    int best = 0;
-    double bc = c64;
-    for (int i = 1; i < 3; ++i) {
-        if ((64 << i) > N) break;
-        const double c = cost(i);
-        if (c < bc && c <= 0.9 * c64) {
-            best = i;
-            bc = c;
-        }
-    }
-    return 64 << best;
-}
-
-// option-kernel threads per task: enough lanes for ceil(nopt/kR) groups, LDS permitting
-#ifndef DH_BIG_TILE_TPT
-#define DH_BIG_TILE_TPT 256   // option threads of tiles of more than 64 options (128: G <= 4 lanes
-#endif                        // per 4-option group on C3's 100-option tiles)
-int option_tpt(int max_nopt, int N, int cap) {
-    int tpt = max_nopt <= kR ? 64 : (max_nopt <= 4 * kR ? 128 : (max_nopt > 64 ? DH_BIG_TILE_TPT : 256));
-    while (tpt < kBlock &&
-           ((size_t)(kBlock / tpt) * option_lds_doubles(N, cap) + (tpt == kBlock ? kRedDoubles : 0)) *
-                   sizeof(double) > (size_t)kLdsDyn)
-        tpt *= 2;
-    return tpt;
-}
-
 }  // namespace
 
-struct GenBufs;                         // dh_gen_device.h
-void gen_bufs_release(dh_ctx* ctx);
-
-struct dh_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    DevBuf params, out, sse, bad, part_sse, part_bad, counter, exact_prices, table, consts, cl_mask,
-        cl_price, aux0, aux1, aux2, aux3, pre;
-    HostBuf h_params, h_loss;  // zero-copy inputs / outputs of small host-API loss requests
-    HostBuf h_pairs;           // zero-copy inputs / outputs of small dh_price_pairs calls
-    DevBuf lb_state, lb_rec, lb_sse, lb_bad, lb_live, lb_done, lb_x0;   // dh_calibrate_lbfgs
-    HostBuf h_lb;              // finished flags / live list of dh_calibrate_lbfgs
-    // the two in-flight slots of dh_surface_fg_begin / _end: zero-copy records in, sse / n_bad
-    // out, the host-side Feller terms and FD steps, and the request's completion event
-    // largest (param sets x tasks) of any dh_surface_fg_begin request on (fg_surf, fg_N): the
-    // scratch reservations are a function of the surface, N and the param-set count only
-    size_t fg_max_units = 0;
-    const dh_surface* fg_surf = nullptr;
-    int fg_N = 0;
-    struct FgSlot {
-        HostBuf h_params, h_loss;
-        std::vector<double> pen, dx;
-        int S = 0, M = 0;
-        const dh_surface* surf = nullptr;   // the surface the request was enqueued on
-        bool pending = false;
-        hipEvent_t done = nullptr;
-    } fg[DH_FG_SLOTS];
-    DevBuf lb_trace, lb_trace_n;   // diagnostic request trace of dh_calibrate_lbfgs
-    hipEvent_t lb_ev[2] = {nullptr, nullptr};   // chunk-completion events of dh_calibrate_lbfgs
-    int64_t lb_trace_cap = 0;
-    bool attr_set = false;
-    dh_ctx_view view;          // resident cos_table_kernel<64/128/256> blocks, whole chip
-    int exact = 0;          // validation mode: every option through the per-term exact path
-    int tail_cut = 1;       // adaptive tail of the angle sums (tail_delta; dh_ctx_set_tail_cut)
-    int path = DH_PATH_AUTO;   // fused / split request kernels (dh_ctx_set_path)
-    int last_path = 0;         // kernels of the last fast-path request (dh_ctx_last_path)
-    int stamps_on = 0;      // diagnostic builds: record per-block phase stamps
-    DevBuf stamps;
-    int64_t stamps_n = 0;
-    // prologues ahead (launch_fused): constants and flags of the later-round tables, the launch
-    // epoch, $DHCOS_AHEAD (-1: not read yet; 0 turns it off) and the resident-block counts of the
-    // fused kernel builds it applies to, by (t1, r1, LDS bytes)
-    DevBuf ahead, ahead_flag;
-    size_t ahead_flag_cap = 0;
-    DevBuf gran;               // tail_sums' granules (partials_only == 3), zeroed on allocation
-    size_t gran_cap = 0;
-    int remap_on = -1;         // $DHCOS_XCD_REMAP: one-round fused grids map blocks to tables by XCD
-                               // (xcd_table; 0 off, 2 multi-round grids too)
-    unsigned ahead_epoch = 0;
-    int ahead_on = -1;
-    // the host copy of the next fused launch's param records (dh_surface_fg_begin sets it
-    // around its launch): fused launches of <= kKargSets records pass them in their kernel
-    // arguments; $DHCOS_KARG_PARAMS=0 turns that off (kp_on: -1 not read yet)
-    const double* kp_src = nullptr;
-    const dh_surface* kp_surf = nullptr;   // and its surface (host copies of the groups)
-    int64_t kp_n = 0;
-    int kp_on = -1;
-    // and its completion event: recorded by the launch itself (hipExtLaunchKernel's stop event)
-    // when the fused kernel is the request's last launch; kp_done_set tells the caller
-    // ($DHCOS_EXT_EVENT=0: a separate hipEventRecord; ext_on: -1 not read yet)
-    hipEvent_t kp_done = nullptr;
-    bool kp_done_set = false;
-    int ext_on = -1;
-    int defer_on = -1;         // $DHCOS_DEFER: multi-round fused loss requests sum their partials
-                               // in the launch's tail (2), in loss_partials_kernel (1) or through
-                               // the ticket hand-off (0); -1: not read yet
-    std::vector<std::pair<std::array<int64_t, 3>, int>> resident_fused;
-    GenBufs* gen = nullptr;    // the generator's device draw (dh_gen_device)
-    DevBuf iv;                 // quote columns / vols of dh_implied_vol, dh_surface_implied_vol
-    DevBuf iv_part_sse, iv_part_bad;   // tile partials of dh_surface_iv_sse_dev (dh_iv_loss.h)
-    DevBuf rows_mkt, rows_row;         // market rows / row of each set (dh_loss_rows.h)
-    // dh_calibrate_lbfgs_batch: the requests' prices, and each start's spot, rate and market
-    DevBuf lb_prices, lb_spot, lb_rate, lb_mof;
-    // the vol-space rows (dh_loss_rows.h): weight rows [B][M], each start's weight sum
-    DevBuf rows_wgt, lb_div;
-    // the Monte Carlo pricer (dh_mc.h): staged records, sorted options / observation steps, the
-    // blocks' partial sums, staged outputs
-    DevBuf mc_params, mc_opts, mc_part, mc_out;
-};
-
-struct dh_surface {
-    dh_ctx* ctx = nullptr;
-    int M = 0;
-    int n_tiles = 0;
-    int n_groups = 0;       // distinct maturities
-    int max_nopt = 0;       // largest tile
-    int max_group = 0;      // largest maturity group
-    int strike_mode = 0;
-    bool has_mkt = false;
-    double* K = nullptr;
-    double* T = nullptr;
-    double* mkt = nullptr;
-    int8_t* call = nullptr;
-    int* perm = nullptr;
-    int2* tiles = nullptr;
-    int* tile_group = nullptr;
-    double* group_T = nullptr;
-    int2* groups = nullptr;
-    void* block = nullptr;  // the one device allocation every array above points into
-    // dh_surface_set_iv_market (dh_iv_loss.h): market vols and weights [M] in the caller's option
-    // order, in an allocation of their own
-    bool has_iv = false;
-    double* iv_mkt = nullptr;
-    double* iv_wgt = nullptr;
-    void* iv_block = nullptr;
-    std::vector<double> h_group_T;   // host copies of group_T / groups (the fused launch's
-    std::vector<int2> h_groups;      // kernel arguments, KargParams)
-};
-
-namespace {
-
-// Requests run the per-term path (cos_exact_kernel) in validation mode, and for series longer
-// than the fast path's LDS-resident table holds (N > DH_MAX_N).
-bool per_term(const dh_ctx* ctx, int N) { return ctx->exact || N > DH_MAX_N; }
-
-// A negative invalid count is tail_sums' timeout marker (a loss hand-off that never completed):
-// an error, not a loss
-int check_loss_counts(const int32_t* n_bad, int64_t S) {
-    for (int64_t i = 0; i < S; ++i)
-        if (n_bad[i] < 0)
-            return fail(DH_E_HIP, "loss hand-off timed out in the fused kernel (param set " +
-                                      std::to_string(i) + ")");
-    return DH_OK;
-}
-
-// Busy-wait for a short request (a calibration iteration waits on it): polling hipStreamQuery
-// returns as soon as the stream drains, where hipStreamSynchronize may yield the thread.
-int spin_sync(hipStream_t st) {
-    for (;;) {
-        const hipError_t e = hipStreamQuery(st);
-        if (e == hipSuccess) return DH_OK;
-        if (e != hipErrorNotReady)
-            return fail(DH_E_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(e));
-    }
-}
-
-}  // namespace
-
-// Makes the context's device current for one C-ABI call and restores the caller's device on
-// return.  The HIP runtime is shared with torch (one libamdhip64 per process), so leaving another
-// device current would move torch's current device under the caller (a rank's RCCL tensors would
-// land on the wrong GPU).
-struct DeviceScope {
-    int prev = -1;
-    int rc = DH_OK;
-    explicit DeviceScope(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev == device) return;
-        const hipError_t e = hipSetDevice(device);
-        if (e != hipSuccess) {
-            rc = fail(DH_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-            prev = -1;
-        }
-    }
-    ~DeviceScope() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-    DeviceScope(const DeviceScope&) = delete;
-    DeviceScope& operator=(const DeviceScope&) = delete;
-};
-
-namespace {
-
-int ensure_attrs(dh_ctx* ctx) {
-    if (ctx->attr_set) return DH_OK;
-    for (const void* f :
-         {(const void*)cos_option_kernel<64, 1>, (const void*)cos_option_kernel<128, 1>,
-          (const void*)cos_option_kernel<256, 1>, (const void*)cos_option_kernel<64, kR>,
-          (const void*)cos_option_kernel<128, kR>, (const void*)cos_option_kernel<256, kR>,
-          (const void*)cos_fused_kernel<64, 1>, (const void*)cos_fused_kernel<128, 1>,
-          (const void*)cos_fused_kernel<256, 1>, (const void*)cos_fused_kernel<64, kR>,
-          (const void*)cos_fused_kernel<128, kR>, (const void*)cos_fused_kernel<256, kR>,
-          (const void*)cos_fused_kernel<64, 1, DH_FUSED_WAVES_WIDE>,
-          (const void*)cos_fused_kernel<128, 1, DH_FUSED_WAVES_WIDE>,
-          (const void*)cos_fused_kernel<256, 1, DH_FUSED_WAVES_WIDE>,
-          (const void*)cos_fused_kernel<64, 1, DH_FUSED_WAVES, true>,
-          (const void*)cos_fused_kernel<128, 1, DH_FUSED_WAVES, true>,
-          (const void*)cos_fused_kernel<256, 1, DH_FUSED_WAVES, true>})
-        HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsDyn));
-    // table-kernel grid = resident capacity (each block then owns a contiguous table range)
-    int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    const void* fns[3] = {(const void*)cos_table_kernel<64>, (const void*)cos_table_kernel<128>,
-                          (const void*)cos_table_kernel<256>};
-    for (int i = 0; i < 3; ++i) {
-        // dynamic LDS at DH_MAX_N (T2 of each wider slot) so the count never overstates
-        const size_t lds = i == 0 ? 0 : (size_t)(kBlock / (64 << i)) * DH_MAX_N * sizeof(double);
-        int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fns[i], kBlock, lds));
-        ctx->view.resident[i] = std::max(1, per_cu) * std::max(1, cus);
-    }
-    const void* gens[3] = {(const void*)cos_gen_kernel<16>, (const void*)cos_gen_kernel<8>,
-                           (const void*)cos_gen_kernel<4>};
-    for (int i = 0; i < 3; ++i) {               // LDS of the largest N each build takes
-        const size_t lds = (size_t)gen_max_n(16 >> i) * (16 >> i) * sizeof(double2);
-        int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gens[i], kBlock, lds));
-        ctx->view.resident_gen[i] = std::max(1, per_cu) * std::max(1, cus);
-    }
-    ctx->attr_set = true;
-    return DH_OK;
-}
-
-int check_N(int N) {
-    if (N < 1 || N > DH_MAX_N_PER_TERM)
-        return fail(DH_E_ARG, "N must be in [1, " + std::to_string(DH_MAX_N_PER_TERM) + "], got " +
-                                  std::to_string(N));
-    return DH_OK;
-}
-
-int launch_exact(dh_ctx* ctx, const PriceArgs& A, hipStream_t st) {
-    const int64_t n_items = A.paired ? A.P : A.P * (int64_t)A.M;
-    double* prices = nullptr;
-    if (A.part_sse) {
-        HIP_TRY(ctx->exact_prices.reserve((size_t)n_items * 8));
-        prices = (double*)ctx->exact_prices.ptr;
-    }
-    const int64_t blocks = (n_items * 64 + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffLL) return fail(DH_E_ARG, "too many items for one launch");
-    hipLaunchKernelGGL(cos_exact_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, A, prices);
-    HIP_TRY(hipGetLastError());
-    if (A.part_sse) {
-        const int64_t S = A.P;
-        hipLaunchKernelGGL(loss_from_prices_kernel, dim3((unsigned)((S * 64 + kBlock - 1) / kBlock)),
-                           dim3(kBlock), 0, st, (const double*)prices, A.mkt, A.M, S, A.sse,
-                           A.n_bad);
-        HIP_TRY(hipGetLastError());
-    }
-    return DH_OK;
-}
-
-constexpr int kZeroCopyMaxSets = 1024;       // host-API loss requests up to this many param sets
-                                             // read / write through mapped host memory
-
-size_t fused_lds_bytes(int N, int cap) {
-    return ((size_t)option_lds_doubles(N, cap) + (size_t)cap + kRedDoubles) * sizeof(double);
-}
-
-#ifndef DH_FUSED_WIDE_MIN_BLOCKS
-#define DH_FUSED_WIDE_MIN_BLOCKS 4096
-#endif
-constexpr int64_t kFusedWideMinBlocks = DH_FUSED_WIDE_MIN_BLOCKS;
-// fused grids from this size take their prologue constants from table_prologue_kernel (C4's
-// 28,672 blocks: 297 -> 285 us; C3's 4,200 lose 3% to the extra launch, C2's 448 its latency)
-#ifndef DH_PROLOGUE_KERNEL_MIN_BLOCKS
-#define DH_PROLOGUE_KERNEL_MIN_BLOCKS 8192
-#endif
-constexpr int64_t kPrologueKernelMinBlocks = DH_PROLOGUE_KERNEL_MIN_BLOCKS;
-
-// One fused launch for the whole request (every group is one tile).
-int launch_fused(dh_ctx* ctx, const PriceArgs& A0, hipStream_t st) {
-    const int N = A0.N;
-    const int tpp = A0.paired ? 1 : A0.n_groups;
-    const int t1 = fused_tpt(N);
-    const int max_nopt = A0.paired ? 1 : A0.opt_cap;
-    const int t2 = option_tpt(max_nopt, N, A0.opt_cap);
-    const size_t lds = fused_lds_bytes(N, A0.opt_cap);
-    const int64_t blocks = A0.P * tpp;
-    if (blocks > 0x7fffffffLL) return fail(DH_E_ARG, "launch too large");
-    PriceArgs A = A0;
-    A.p0 = 0;
-    A.np = A0.P;
-    if (ctx->stamps_on) {
-        HIP_TRY(ctx->stamps.reserve((size_t)blocks * kStamps * 8));
-        HIP_TRY(hipMemsetAsync(ctx->stamps.ptr, 0, (size_t)blocks * kStamps * 8, st));
-        ctx->stamps_n = blocks * kStamps;
-        A.stamps = (unsigned long long*)ctx->stamps.ptr;
-    }
-    const dim3 grid((unsigned)blocks), block((unsigned)std::max(t1, t2));
-    const double* tsrc = A.paired ? A.T : A.group_T;       // FusedHead: preloaded arguments
-    const bool r1 = tile_r(max_nopt, t2) == 1;
-    A.ahead = nullptr;
-    A.ahead_flag = nullptr;
-    A.ahead_stride = 0;
-    A.gran = nullptr;
-    if (ctx->remap_on < 0) {
-        const char* e = std::getenv("DHCOS_XCD_REMAP");
-        ctx->remap_on = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1;
-    }
-    // by XCD: one-round grids of more than one maturity group (below); multi-round grids (C3)
-    // measured slower with it (57.7 vs 56.5 us per request), one-round C2 0.15 us faster
-    A.remap = 0;
-    bool remap_ok = ctx->remap_on && !A.paired && tpp > 1;
-    if (ctx->ahead_on < 0) {
-        const char* e = std::getenv("DHCOS_AHEAD");
-        ctx->ahead_on = (e && e[0] == '0') ? 0 : 1;
-    }
-    // prologues ahead: the 4-wave build of >= 3-wave blocks, more blocks than one round of
-    // resident ones, in-block prologues (no prologue kernel)
-    const bool wide = r1 && blocks >= kFusedWideMinBlocks;
-    if (ctx->ahead_on && !wide && block.x >= 192 && blocks < kPrologueKernelMinBlocks) {
-        const std::array<int64_t, 3> key{t1, r1 ? 1 : 0, (int64_t)lds};
-        int res = -1;
-        for (const auto& kv : ctx->resident_fused)
-            if (kv.first == key) res = kv.second;
-        if (res < 0) {
-            const void* f = nullptr;
-            switch (t1 * (r1 ? 1 : -1)) {
-                case 64: f = (const void*)cos_fused_kernel<64, 1>; break;
-                case 128: f = (const void*)cos_fused_kernel<128, 1>; break;
-                case 256: f = (const void*)cos_fused_kernel<256, 1>; break;
-                case -64: f = (const void*)cos_fused_kernel<64, kR>; break;
-                case -128: f = (const void*)cos_fused_kernel<128, kR>; break;
-                default: f = (const void*)cos_fused_kernel<256, kR>; break;
-            }
-            int per_cu = 0, cus = 0;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, (int)block.x, lds));
-            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-            res = std::max(1, per_cu) * std::max(1, cus);
-            ctx->resident_fused.push_back({key, res});
-        }
-        if (ctx->defer_on < 0) {
-            const char* e = std::getenv("DHCOS_DEFER");
-            ctx->defer_on = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2;
-        }
-        const int defer = ctx->defer_on;
-        if (blocks > res) {
-            const size_t slots = (size_t)blocks;
-            HIP_TRY(ctx->ahead.reserve(slots * kAheadRec * sizeof(double)));
-            if (slots > ctx->ahead_flag_cap) {
-                HIP_TRY(ctx->ahead_flag.reserve(slots * sizeof(unsigned long long)));
-                HIP_TRY(hipMemsetAsync(ctx->ahead_flag.ptr, 0, ctx->ahead_flag.cap, st));
-                ctx->ahead_flag_cap = ctx->ahead_flag.cap / sizeof(unsigned long long);
-            }
-            if (++ctx->ahead_epoch == 0) ++ctx->ahead_epoch;     // 0: the cleared flags' value
-            A.ahead = (double*)ctx->ahead.ptr;
-            A.ahead_flag = (unsigned long long*)ctx->ahead_flag.ptr;
-            A.ahead_stride = res;
-            A.ahead_epoch = ctx->ahead_epoch;
-            if (ctx->remap_on == 2 && remap_ok) A.remap = 1;   // C3 +1.1 us: off by default
-            // and the loss sums deferred (below), or in loss_partials_kernel ($DHCOS_DEFER=1)
-            if (defer == 1 && A.part_sse && !A.partials_only && !A.paired) {
-                // (partial, invalid count) pairs: 16 bytes per task
-                HIP_TRY(ctx->part_sse.reserve((size_t)A.P * A.n_tiles * 2 * sizeof(double)));
-                A.part_sse = (double*)ctx->part_sse.ptr;
-                A.partials_only = 2;
-            }
-        } else if (remap_ok) {
-            A.remap = 1;                         // one round of resident blocks
-        }
-        // loss sums in the launch's tail ($DHCOS_DEFER=2, the default; 0: the hand-off's ticket in
-        // every block): C3 -1.1 us against loss_partials_kernel, C2 (one round) -0.5 us against
-        // the ticket.  At most a quarter of the resident blocks wait (tail_sums)
-        if (defer == 2 && A.part_sse && !A.partials_only && !A.paired && A.P <= res / 4 &&
-            A.max_group < (1 << kGranCountBits)) {
-            if (A.ahead_stride == 0 && ++ctx->ahead_epoch == 0) ++ctx->ahead_epoch;
-            A.ahead_epoch = ctx->ahead_epoch;
-            const int64_t tasks = A.P * A.n_tiles;
-            if ((size_t)tasks > ctx->gran_cap) {    // two granules per task, zeroed (no epoch is 0)
-                HIP_TRY(ctx->gran.reserve((size_t)tasks * 2 * sizeof(unsigned long long)));
-                HIP_TRY(hipMemsetAsync(ctx->gran.ptr, 0, ctx->gran.cap, st));
-                ctx->gran_cap = ctx->gran.cap / (2 * sizeof(unsigned long long));
-            }
-            A.gran = (unsigned long long*)ctx->gran.ptr;
-            A.partials_only = 3;
-        }
-    }
-    if (blocks >= kPrologueKernelMinBlocks && !ctx->stamps_on) {
-        HIP_TRY(ctx->pre.reserve((size_t)blocks * kTabC * sizeof(double)));
-        A.pre = (const double*)ctx->pre.ptr;
-        hipLaunchKernelGGL(table_prologue_kernel,
-                           dim3((unsigned)((blocks * kPreLanes + kBlock - 1) / kBlock)),
-                           dim3(kBlock), 0, st, A, blocks, (double*)ctx->pre.ptr);
-        HIP_TRY(hipGetLastError());
-    }
-    // small requests whose records were handed over from the host (dh_surface_fg_begin): the
-    // records in the kernel arguments (in-block-prologue launches of the 4-wave build)
-    if (ctx->kp_on < 0) {
-        const char* e = std::getenv("DHCOS_KARG_PARAMS");
-        ctx->kp_on = (e && e[0] == '0') ? 0 : 1;
-    }
-    if (ctx->kp_on && ctx->kp_src && ctx->kp_surf && !A.paired &&
-        (int)ctx->kp_surf->h_group_T.size() == tpp && tpp <= kKargGroups &&
-        A.P == ctx->kp_n && A.P <= kKargSets && r1 && !wide &&
-        blocks < kPrologueKernelMinBlocks && !ctx->stamps_on && !A.exact) {
-        KargParams pb{};
-        std::memcpy(pb.v, ctx->kp_src, (size_t)A.P * DH_PARAM_STRIDE * sizeof(double));
-        std::memcpy(pb.T, ctx->kp_surf->h_group_T.data(), (size_t)tpp * sizeof(double));
-        std::memcpy(pb.groups, ctx->kp_surf->h_groups.data(), (size_t)tpp * sizeof(int2));
-        if (ctx->ext_on < 0) {
-            const char* e = std::getenv("DHCOS_EXT_EVENT");
-            ctx->ext_on = (e && e[0] == '0') ? 0 : 1;
-        }
-        hipEvent_t stop = (ctx->ext_on && A.partials_only != 2) ? ctx->kp_done : nullptr;
-        switch (t1) {
-            case 64: hipExtLaunchKernelGGL((cos_fused_kernel<64, 1, DH_FUSED_WAVES, true>), grid, block, lds, st, nullptr, stop, 0, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, pb); break;
-            case 128: hipExtLaunchKernelGGL((cos_fused_kernel<128, 1, DH_FUSED_WAVES, true>), grid, block, lds, st, nullptr, stop, 0, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, pb); break;
-            default: hipExtLaunchKernelGGL((cos_fused_kernel<256, 1, DH_FUSED_WAVES, true>), grid, block, lds, st, nullptr, stop, 0, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, pb); break;
-        }
-        HIP_TRY(hipGetLastError());
-        ctx->kp_done_set = stop != nullptr;
-        if (A.partials_only == 2) {
-            hipLaunchKernelGGL(loss_partials_kernel, dim3((unsigned)A.P), dim3(64), 0, st,
-                               (const double2*)A.part_sse, A.n_tiles, A.sse, A.n_bad);
-            HIP_TRY(hipGetLastError());
-        }
-        return DH_OK;
-    }
-    // grids of many small blocks (C4: 28,672) gain from a fifth wave per SIMD to overlap the
-    // blocks' latency-bound phases; small grids keep the 4-wave build, whose blocks are shorter
-    // (same arithmetic: only the register allocation differs, so the same bits)
-    if (r1 && blocks >= kFusedWideMinBlocks) {
-        switch (t1) {
-            case 64: hipLaunchKernelGGL((cos_fused_kernel<64, 1, DH_FUSED_WAVES_WIDE>), grid, block, lds, st, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, NoKargParams{}); break;
-            case 128: hipLaunchKernelGGL((cos_fused_kernel<128, 1, DH_FUSED_WAVES_WIDE>), grid, block, lds, st, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, NoKargParams{}); break;
-            default: hipLaunchKernelGGL((cos_fused_kernel<256, 1, DH_FUSED_WAVES_WIDE>), grid, block, lds, st, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, NoKargParams{}); break;
-        }
-        HIP_TRY(hipGetLastError());
-        return DH_OK;
-    }
-    switch (t1 * (r1 ? 1 : -1)) {
-        case 64: hipLaunchKernelGGL((cos_fused_kernel<64, 1>), grid, block, lds, st, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, NoKargParams{}); break;
-        case 128: hipLaunchKernelGGL((cos_fused_kernel<128, 1>), grid, block, lds, st, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, NoKargParams{}); break;
-        case 256: hipLaunchKernelGGL((cos_fused_kernel<256, 1>), grid, block, lds, st, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, NoKargParams{}); break;
-        case -64: hipLaunchKernelGGL((cos_fused_kernel<64, kR>), grid, block, lds, st, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, NoKargParams{}); break;
-        case -128: hipLaunchKernelGGL((cos_fused_kernel<128, kR>), grid, block, lds, st, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, NoKargParams{}); break;
-        default: hipLaunchKernelGGL((cos_fused_kernel<256, kR>), grid, block, lds, st, A.prm, tsrc, A.groups, A.live_count, A.pre, tpp, A.paired, A, t2, NoKargParams{}); break;
-    }
-    HIP_TRY(hipGetLastError());
-    if (A.partials_only == 2) {
-        hipLaunchKernelGGL(loss_partials_kernel, dim3((unsigned)A.P), dim3(64), 0, st,
-                           (const double2*)A.part_sse, A.n_tiles, A.sse, A.n_bad);
-        HIP_TRY(hipGetLastError());
-    }
-    return DH_OK;
-}
-
-// The generator batch path: every maturity group one tile of <= kSmallTile options, a large call
-// (DESIGN.md 3.3): one persistent cos_gen_kernel launch for the whole request.
-int launch_gen(dh_ctx* ctx, const PriceArgs& A0, hipStream_t st, int TB) {
-    const int tpp = A0.paired ? 1 : A0.n_groups;
-    const int max_nopt = A0.paired ? 1 : A0.opt_cap;
-    int OP = 1;
-    while (OP < max_nopt) OP *= 2;
-    PriceArgs A = A0;
-    A.p0 = 0;
-    A.np = A0.P;
-    A.partials_only = 0;
-    const int64_t n_q = A.np * tpp;
-    const int gi = TB == 16 ? 0 : (TB == 8 ? 1 : 2);
-    const int64_t blocks = std::min<int64_t>((n_q + TB - 1) / TB, ctx->view.resident_gen[gi]);
-    const size_t lds = (size_t)TB * A.N * sizeof(double2);
-    if (blocks <= 0 || OP > kBlock / TB) return fail(DH_E_ARG, "generator kernel shape");
-    switch (TB) {
-        case 16: hipLaunchKernelGGL((cos_gen_kernel<16>), dim3((unsigned)blocks), dim3(kBlock), lds, st, A, OP); break;
-        case 8: hipLaunchKernelGGL((cos_gen_kernel<8>), dim3((unsigned)blocks), dim3(kBlock), lds, st, A, OP); break;
-        default: hipLaunchKernelGGL((cos_gen_kernel<4>), dim3((unsigned)blocks), dim3(kBlock), lds, st, A, OP); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-
-// Table kernel then option kernel per chunk of param sets; the chunk keeps the table workspace
-// within kTableBudget (L2/MALL-resident between the two launches).  Requests whose maturity
-// groups are single tiles may instead run as one fused launch (ctx->path).
-int launch_price(dh_ctx* ctx, const PriceArgs& A_in, hipStream_t st) {
-    PriceArgs A0 = A_in;
-    A0.tail = ctx->tail_cut ? kTailScale : -1.0;
-    const int64_t tasks_per_p = A0.paired ? 1 : A0.n_tiles;
-    if (A0.P * tasks_per_p == 0) return DH_OK;
-    if (A0.exact) return launch_exact(ctx, A0, st);
-    int rc = ensure_attrs(ctx);
-    if (rc) return rc;
-    const int N = A0.N;
-    {
-        const int max_nopt = A0.paired ? 1 : A0.opt_cap;
-        const bool small_call = max_nopt <= kSmallTile && A0.P * tasks_per_p >= kSmallMinTasks;
-        const bool fusable = (A0.paired || A0.max_group <= kTileMax) &&
-                             fused_lds_bytes(N, A0.opt_cap) <= (size_t)kLdsDyn;
-        // auto: fused wherever it applies except small tiles in large calls (generator grids,
-        // whose lane-per-option-group kernel is 1.7x faster); measured on the current kernels:
-        // C3 113 vs 133 us, C4 393 vs 407 us per request
-        const bool fused = fusable && (ctx->path == DH_PATH_FUSED ||
-                                       (ctx->path == DH_PATH_AUTO && !small_call));
-        ctx->last_path = fused ? DH_PATH_FUSED : DH_PATH_SPLIT;
-        if (fused) return launch_fused(ctx, A0, st);
-        // generator grids: one fused small-tile launch (PATH_SPLIT keeps the table + option
-        // kernels, for A/B)
-        const int tb = gen_tb(N);
-        if (small_call && ctx->path == DH_PATH_AUTO && tb &&
-            (A0.paired || A0.n_tiles == A0.n_groups)) {
-            ctx->last_path = DH_PATH_GEN;
-            return launch_gen(ctx, A0, st, tb);
-        }
-    }
-    const int tpp = A0.paired ? 1 : A0.n_groups;
-    const int words = cl_words(A0);
-    const size_t per_p =
-        (size_t)tpp * ((size_t)N + kConsts + words + (size_t)A0.max_group) * sizeof(double);
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(A0.P, kTableBudget / per_p));
-    // rounded up to whole kTabTile-table tiles (the small-tile kernel's layout)
-    HIP_TRY(ctx->table.reserve((size_t)((chunk * tpp + kTabTile - 1) / kTabTile) * kTabTile * N *
-                               sizeof(double)));
-    HIP_TRY(ctx->consts.reserve((size_t)chunk * tpp * kConsts * sizeof(double)));
-    HIP_TRY(ctx->cl_mask.reserve((size_t)chunk * tpp * words * 8));
-    HIP_TRY(ctx->cl_price.reserve((size_t)chunk * tpp * A0.max_group * sizeof(double)));
-    // Few tables per resident slot (< 2, e.g. C3's 4,200 tables on 3,072 one-wave slots): one
-    // block per kTabs tables, not persistent, so the dispatcher backfills CUs as blocks finish
-    // instead of fixing each block's share up front (a 5-vs-6-table tail cost C3 ~30% of the
-    // table kernel).  Otherwise a resident grid of persistent blocks and the slot width of
-    // table_tpt.
-    const int64_t nq_max = std::min<int64_t>(A0.P, chunk) * tpp;
-    const bool backfill = nq_max < 2 * (int64_t)ctx->view.resident[0] * (kBlock / 64);
-    const int t1 = backfill ? 64 : table_tpt(ctx->view, nq_max, N);
-    const size_t lds1 = t1 == 64 ? 0 : (size_t)(kBlock / t1) * N * sizeof(double);
-    const int max_nopt = A0.paired ? 1 : A0.opt_cap;
-    // small tiles in a large call take the lane-per-option-group kernel (decided once per call,
-    // so every chunk of it runs the same arithmetic)
-    const bool small = max_nopt <= kSmallTile && A0.P * tasks_per_p >= kSmallMinTasks;
-    const int rs = small_rs(max_nopt);
-    int L = 1;
-    while (L * rs < max_nopt) L *= 2;
-    const int t2 = small ? kBlock : option_tpt(max_nopt, N, A0.opt_cap);
-    const size_t lds2 =
-        small ? 0 : ((size_t)(kBlock / t2) * option_lds_doubles(N, A0.opt_cap) +
-                     (t2 == kBlock ? kRedDoubles : 0)) * sizeof(double);
-    if (lds2 > (size_t)kLdsDyn) return fail(DH_E_ARG, "COS table does not fit in LDS");
-    if (ctx->stamps_on) {
-        const int64_t nb = std::max((chunk * tasks_per_p + kBlock / t2 - 1) / (kBlock / t2),
-                                    (chunk * tpp + kBlock / t1 - 1) / (kBlock / t1));
-        HIP_TRY(ctx->stamps.reserve((size_t)nb * kStamps * 8));
-        HIP_TRY(hipMemsetAsync(ctx->stamps.ptr, 0, (size_t)nb * kStamps * 8, st));
-        ctx->stamps_n = nb * kStamps;
-    }
-    for (int64_t p0 = 0; p0 < A0.P; p0 += chunk) {
-        PriceArgs A = A0;
-        A.partials_only = 0;        // the split kernels always finish the loss hand-off
-        A.p0 = p0;
-        A.np = std::min<int64_t>(chunk, A0.P - p0);
-        A.table = (double*)ctx->table.ptr;
-        A.table_tiled = small ? 1 : 0;
-        A.consts = (double*)ctx->consts.ptr;
-        A.cl_mask = (unsigned long long*)ctx->cl_mask.ptr;
-        A.cl_price = (double*)ctx->cl_price.ptr;
-        A.stamps = ctx->stamps_on ? (unsigned long long*)ctx->stamps.ptr : nullptr;
-        const int64_t n_q = A.np * tpp;
-        const int res = ctx->view.resident[t1 == 64 ? 0 : (t1 == 128 ? 1 : 2)];
-        const int64_t b1 = backfill ? (n_q + kBlock / t1 - 1) / (kBlock / t1)
-                                    : std::min<int64_t>((n_q + kBlock / t1 - 1) / (kBlock / t1), res);
-        const int64_t n_t = A.np * tasks_per_p;
-        const int64_t b2 = small ? (n_t * L + kBlock - 1) / kBlock
-                                 : (n_t + kBlock / t2 - 1) / (kBlock / t2);
-        if (b1 > 0x7fffffffLL || b2 > 0x7fffffffLL) return fail(DH_E_ARG, "launch too large");
-        switch (t1) {
-            case 64: hipLaunchKernelGGL(cos_table_kernel<64>, dim3((unsigned)b1), dim3(kBlock), 0, st, A); break;
-            case 128: hipLaunchKernelGGL(cos_table_kernel<128>, dim3((unsigned)b1), dim3(kBlock), lds1, st, A); break;
-            default: hipLaunchKernelGGL(cos_table_kernel<256>, dim3((unsigned)b1), dim3(kBlock), lds1, st, A); break;
-        }
-        HIP_TRY(hipGetLastError());
-        if (small) {
-            if (rs == 8)
-                hipLaunchKernelGGL((cos_option_small_kernel<8>), dim3((unsigned)b2), dim3(kBlock), 0, st, A, L);
-            else
-                hipLaunchKernelGGL((cos_option_small_kernel<4>), dim3((unsigned)b2), dim3(kBlock), 0, st, A, L);
-        } else {
-            const dim3 g2((unsigned)b2), bk(kBlock);
-            switch (t2 * (tile_r(max_nopt, t2) == 1 ? 1 : -1)) {
-                case 64: hipLaunchKernelGGL((cos_option_kernel<64, 1>), g2, bk, lds2, st, A); break;
-                case 128: hipLaunchKernelGGL((cos_option_kernel<128, 1>), g2, bk, lds2, st, A); break;
-                case 256: hipLaunchKernelGGL((cos_option_kernel<256, 1>), g2, bk, lds2, st, A); break;
-                case -64: hipLaunchKernelGGL((cos_option_kernel<64, kR>), g2, bk, lds2, st, A); break;
-                case -128: hipLaunchKernelGGL((cos_option_kernel<128, kR>), g2, bk, lds2, st, A); break;
-                default: hipLaunchKernelGGL((cos_option_kernel<256, kR>), g2, bk, lds2, st, A); break;
-            }
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    return DH_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int dh_version(void) { return 1; }
-
-const char* dh_last_error(void) { return g_err.c_str(); }
-
-int dh_device_count(int* count) {
-    if (!count) return fail(DH_E_ARG, "count is null");
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) {
-        *count = 0;
-        return fail(DH_E_NODEV, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
-    }
-    *count = n;
-    return DH_OK;
-}
-
-int dh_ctx_create(int device, dh_ctx** out) {
-    if (!out) return fail(DH_E_ARG, "out is null");
-    *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n == 0)
-        return fail(DH_E_NODEV, std::string("no HIP device: ") + hipGetErrorString(e));
-    if (device < 0 || device >= n) return fail(DH_E_ARG, "device index out of range");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(DH_E_NODEV, std::string("libdhcos is built for gfx950, device is ") +
-                                    prop.gcnArchName);
-    dh_ctx* c = new (std::nothrow) dh_ctx();
-    if (!c) return fail(DH_E_ALLOC, "ctx alloc");
-    c->device = device;
-    DeviceScope dev_scope(device);
-    if (dev_scope.rc) {
-        delete c;
-        return dev_scope.rc;
-    }
-    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete c;
-        return fail(DH_E_HIP, std::string("stream create: ") + hipGetErrorString(e));
-    }
-    *out = c;
-    return DH_OK;
-}
-
-int dh_ctx_destroy(dh_ctx* ctx) {
-    if (!ctx) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (DevBuf* b : {&ctx->params, &ctx->out, &ctx->sse, &ctx->bad, &ctx->part_sse,
-                      &ctx->part_bad, &ctx->counter, &ctx->exact_prices, &ctx->stamps, &ctx->table,
-                      &ctx->consts, &ctx->cl_mask, &ctx->cl_price, &ctx->aux0,
-                      &ctx->aux1, &ctx->aux2, &ctx->aux3, &ctx->pre, &ctx->lb_state, &ctx->lb_rec,
-                      &ctx->lb_sse, &ctx->lb_bad, &ctx->lb_live, &ctx->lb_done, &ctx->lb_x0,
-                      &ctx->lb_trace, &ctx->lb_trace_n, &ctx->iv, &ctx->iv_part_sse,
-                      &ctx->iv_part_bad, &ctx->rows_mkt, &ctx->rows_row, &ctx->lb_prices,
-                      &ctx->lb_spot, &ctx->lb_rate, &ctx->lb_mof, &ctx->rows_wgt,
-                      &ctx->lb_div, &ctx->mc_params, &ctx->mc_opts, &ctx->mc_part, &ctx->mc_out})
-        b->release();
-    ctx->h_params.release();
-    ctx->h_loss.release();
-    ctx->h_lb.release();
-    ctx->h_pairs.release();
-    for (hipEvent_t e : ctx->lb_ev)
-        if (e) (void)hipEventDestroy(e);
-    gen_bufs_release(ctx);
-    for (auto& F : ctx->fg) {
-        F.h_params.release();
-        F.h_loss.release();
-        if (F.done) (void)hipEventDestroy(F.done);
-    }
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-    return DH_OK;
-}
-
-int dh_ctx_synchronize(dh_ctx* ctx) {
-    if (!ctx) return fail(DH_E_ARG, "ctx is null");
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return DH_OK;
-}
-
-void* dh_ctx_stream(dh_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
-
-int dh_ctx_debug_stamps(dh_ctx* ctx, int on) {
-    if (!ctx) return fail(DH_E_ARG, "ctx is null");
-#ifdef DH_STAMPS
-    ctx->stamps_on = on ? 1 : 0;
-    return DH_OK;
-#else
-    (void)on;
-    return fail(DH_E_ARG, "library built without DH_STAMPS (use `make stamps`)");
-#endif
-}
-
-int dh_ctx_read_stamps(dh_ctx* ctx, unsigned long long* out, int64_t cap, int64_t* n) {
-    if (!ctx || !n) return fail(DH_E_ARG, "null argument");
-    *n = ctx->stamps_n;
-    if (!out || ctx->stamps_n == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, ctx->stamps.ptr, (size_t)std::min<int64_t>(cap, ctx->stamps_n) * 8,
-                      hipMemcpyDeviceToHost));
-    return DH_OK;
-}
-
-int dh_ctx_set_path(dh_ctx* ctx, int path) {
-    if (!ctx) return fail(DH_E_ARG, "ctx is null");
-    if (path != DH_PATH_AUTO && path != DH_PATH_SPLIT && path != DH_PATH_FUSED)
-        return fail(DH_E_ARG, "bad path");
-    ctx->path = path;
-    return DH_OK;
-}
-
-int dh_ctx_last_path(dh_ctx* ctx) { return ctx ? ctx->last_path : DH_E_ARG; }
-
-int dh_ctx_set_exact(dh_ctx* ctx, int on) {
-    if (!ctx) return fail(DH_E_ARG, "ctx is null");
-    ctx->exact = on ? 1 : 0;
-    return DH_OK;
-}
-
-int dh_ctx_set_tail_cut(dh_ctx* ctx, int on) {
-    if (!ctx) return fail(DH_E_ARG, "ctx is null");
-    ctx->tail_cut = on ? 1 : 0;
-    return DH_OK;
-}
-
-int dh_surface_create(dh_ctx* ctx, const double* K, const double* T, const int8_t* is_call,
-                      const double* mkt, int M, int strike_mode, dh_surface** out) {
-    if (!ctx || !out) return fail(DH_E_ARG, "ctx/out is null");
-    *out = nullptr;
-    if (M < 0) return fail(DH_E_ARG, "M < 0");
-    if (M > 0 && (!K || !T || !is_call)) return fail(DH_E_ARG, "K/T/is_call is null");
-    if (strike_mode != DH_STRIKE_ABSOLUTE && strike_mode != DH_STRIKE_PCT_SPOT)
-        return fail(DH_E_ARG, "bad strike_mode");
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    // group by exact maturity (stable), cut groups into tiles of <= kTileMax options
-    std::vector<int> perm(M);
-    std::iota(perm.begin(), perm.end(), 0);
-    std::stable_sort(perm.begin(), perm.end(), [&](int i, int j) { return T[i] < T[j]; });
-    std::vector<double> sK(M), sT(M), sm(M, 0.0);
-    std::vector<int8_t> sc(M);
-    for (int i = 0; i < M; ++i) {
-        sK[i] = K[perm[i]];
-        sT[i] = T[perm[i]];
-        sc[i] = is_call[perm[i]] ? 1 : 0;
-        if (mkt) sm[i] = mkt[perm[i]];
-    }
-    std::vector<int2> tiles;
-    std::vector<int> tile_group;
-    std::vector<double> group_T;
-    std::vector<int2> groups;
-    int max_nopt = 0, max_group = 0;
-    for (int i = 0; i < M;) {
-        int j = i;
-        while (j < M && sT[j] == sT[i]) ++j;
-        groups.push_back(make_int2(i, j - i));
-        max_group = std::max(max_group, j - i);
-        for (int s = i; s < j; s += kTileMax) {
-            tiles.push_back(make_int2(s, std::min(kTileMax, j - s)));
-            tile_group.push_back((int)group_T.size());
-            max_nopt = std::max(max_nopt, std::min(kTileMax, j - s));
-        }
-        group_T.push_back(sT[i]);
-        i = j;
-    }
-    dh_surface* s = new (std::nothrow) dh_surface();
-    if (!s) return fail(DH_E_ALLOC, "surface alloc");
-    s->ctx = ctx;
-    s->M = M;
-    s->n_tiles = (int)tiles.size();
-    s->n_groups = (int)group_T.size();
-    s->max_nopt = max_nopt;
-    s->max_group = max_group;
-    s->strike_mode = strike_mode;
-    s->has_mkt = mkt != nullptr;
-    s->h_group_T = group_T;
-    s->h_groups = groups;
-    // every array in one device allocation, staged on the host and uploaded by one copy (one
-    // hipMalloc and one synchronous copy instead of nine of each: ~0.5 ms of a C3 calibration)
-    struct Part {
-        void** dst;
-        const void* src;
-        size_t bytes;
-    };
-    const size_t m = (size_t)M;
-    const Part parts[] = {{(void**)&s->K, sK.data(), m * 8},
-                          {(void**)&s->T, sT.data(), m * 8},
-                          {(void**)&s->mkt, sm.data(), m * 8},
-                          {(void**)&s->call, sc.data(), m},
-                          {(void**)&s->perm, perm.data(), m * 4},
-                          {(void**)&s->tiles, tiles.data(), tiles.size() * sizeof(int2)},
-                          {(void**)&s->tile_group, tile_group.data(), tile_group.size() * sizeof(int)},
-                          {(void**)&s->group_T, group_T.data(), group_T.size() * sizeof(double)},
-                          {(void**)&s->groups, groups.data(), groups.size() * sizeof(int2)}};
-    size_t off[9], total = 0;
-    for (int i = 0; i < 9; ++i) {          // 256-byte aligned, >= 16 bytes each (empty surfaces)
-        off[i] = total;
-        total += (std::max<size_t>(parts[i].bytes, 16) + 255) & ~(size_t)255;
-    }
-    hipError_t e = hipMalloc(&s->block, total);
-    if (e == hipSuccess) {
-        for (int i = 0; i < 9; ++i) *parts[i].dst = (char*)s->block + off[i];
-        if (M > 0) {
-            std::vector<char> stage(total, 0);
-            for (int i = 0; i < 9; ++i)
-                if (parts[i].bytes) std::memcpy(stage.data() + off[i], parts[i].src, parts[i].bytes);
-            e = hipMemcpy(s->block, stage.data(), total, hipMemcpyHostToDevice);
-        }
-    }
-    if (e != hipSuccess) {
-        dh_surface_destroy(s);
-        return fail(DH_E_HIP, std::string("surface upload: ") + hipGetErrorString(e));
-    }
-    *out = s;
-    return DH_OK;
-}
-
-int dh_surface_destroy(dh_surface* s) {
-    if (!s) return DH_OK;
-    DeviceScope dev_scope(s->ctx ? s->ctx->device : 0);
-    if (s->block) (void)hipFree(s->block);
-    if (s->iv_block) (void)hipFree(s->iv_block);
-    delete s;
-    return DH_OK;
-}
-
-int dh_surface_size(const dh_surface* s, int* M, int* n_tiles) {
-    if (!s) return fail(DH_E_ARG, "surface is null");
-    if (M) *M = s->M;
-    if (n_tiles) *n_tiles = s->n_tiles;
-    return DH_OK;
-}
-
-static PriceArgs surface_args(const dh_surface* s, const double* d_params, int64_t P, int N,
-                              double L) {
-    PriceArgs A{};
-    A.prm = d_params;
-    A.P = P;
-    A.K = s->K;
-    A.T = s->T;
-    A.call = s->call;
-    A.mkt = s->mkt;
-    A.perm = s->perm;
-    A.tiles = s->tiles;
-    A.tile_group = s->tile_group;
-    A.group_T = s->group_T;
-    A.groups = s->groups;
-    A.max_group = s->max_group;
-    A.n_tiles = s->n_tiles;
-    A.n_groups = s->n_groups;
-    A.opt_cap = ((s->max_nopt + 1) / 2) * 2;
-    A.M = s->M;
-    A.paired = 0;
-    A.strike_mode = s->strike_mode;
-    A.N = N;
-    A.L = L;
-    A.out_stride = s->M;
-    return A;
-}
-
-int dh_surface_price_dev(dh_ctx* ctx, const dh_surface* s, const double* d_params, int64_t P,
-                         int N, double L, double* d_out, void* stream) {
-    if (!ctx || !s || (P > 0 && (!d_params || !d_out))) return fail(DH_E_ARG, "null argument");
-    int rc = check_N(N);
-    if (rc) return rc;
-    if (P < 0) return fail(DH_E_ARG, "P < 0");
-    if (P == 0 || s->M == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    PriceArgs A = surface_args(s, d_params, P, N, L);
-    A.exact = per_term(ctx, N);
-    A.out = d_out;
-    return launch_price(ctx, A, stream ? (hipStream_t)stream : ctx->stream);
-}
-
-}  // extern "C"
-
-// dh_surface_price_dev for the batch driver's requests (dh_calibrate_lbfgs_batch): a no-op once
-// *live_count is 0, and the kernel choice does not follow the request's size -- under
-// DH_PATH_AUTO the fused kernels wherever they apply, so a start's prices have the same bits
-// whatever shares its launch (the generator kernel of large calls rounds differently, 3.3)
-static int surface_price_launch_lb(dh_ctx* ctx, const dh_surface* s, const double* d_params,
-                                   int64_t P, int N, double L, double* d_out, hipStream_t st,
-                                   const int* live_count) {
-    if (P == 0 || s->M == 0) return DH_OK;
-    PriceArgs A = surface_args(s, d_params, P, N, L);
-    A.exact = per_term(ctx, N);
-    A.out = d_out;
-    A.live_count = live_count;
-    const int path = ctx->path;
-    if (path == DH_PATH_AUTO) ctx->path = DH_PATH_FUSED;
-    const int rc = launch_price(ctx, A, st);
-    ctx->path = path;
-    return rc;
-}
-
-static int surface_loss_launch(dh_ctx* ctx, const dh_surface* s, const double* d_params, int S,
-                               int N, double L, double* d_sse, int32_t* d_n_bad,
-                               double* d_prices, void* stream, const int* live_count,
-                               bool partials_only = false) {
-    if (!ctx || !s || (S > 0 && (!d_params || !d_sse || !d_n_bad)))
-        return fail(DH_E_ARG, "null argument");
-    if (!s->has_mkt) return fail(DH_E_ARG, "surface has no market prices");
-    int rc = check_N(N);
-    if (rc) return rc;
-    if (S < 0) return fail(DH_E_ARG, "S < 0");
-    if (S == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    if (s->M == 0) {
-        HIP_TRY(hipMemsetAsync(d_sse, 0, (size_t)S * 8, st));
-        HIP_TRY(hipMemsetAsync(d_n_bad, 0, (size_t)S * 4, st));
-        return DH_OK;
-    }
-    const size_t nparts = (size_t)S * s->n_tiles;
-    HIP_TRY(ctx->part_sse.reserve(nparts * 8));
-    HIP_TRY(ctx->part_bad.reserve(nparts * 4));
-    const size_t cap0 = ctx->counter.cap;
-    HIP_TRY(ctx->counter.reserve((size_t)S * kCounterStride * 4));
-    if (ctx->counter.cap != cap0) {       // fresh counters start at zero; kernels self-reset
-        HIP_TRY(hipMemsetAsync(ctx->counter.ptr, 0, ctx->counter.cap, st));
-    }
-    PriceArgs A = surface_args(s, d_params, S, N, L);
-    A.exact = per_term(ctx, N);
-    A.out = d_prices;
-    A.part_sse = (double*)ctx->part_sse.ptr;
-    A.part_bad = (int*)ctx->part_bad.ptr;
-    A.counter = (unsigned*)ctx->counter.ptr;
-    A.sse = d_sse;
-    A.n_bad = (int*)d_n_bad;
-    A.live_count = live_count;
-    A.partials_only = partials_only && !A.exact ? 1 : 0;
-    A.host_out = ctx->kp_src != nullptr;     // the host API's zero-copy requests (kp_src set)
-    return launch_price(ctx, A, st);
-}
-
-extern "C" {
-
-int dh_surface_loss_dev(dh_ctx* ctx, const dh_surface* s, const double* d_params, int S, int N,
-                        double L, double* d_sse, int32_t* d_n_bad, double* d_prices,
-                        void* stream) {
-    return surface_loss_launch(ctx, s, d_params, S, N, L, d_sse, d_n_bad, d_prices, stream,
-                               nullptr);
-}
-
-int dh_surface_price(dh_ctx* ctx, const dh_surface* s, const double* params, int64_t P, int N,
-                     double L, double* out) {
-    if (!ctx || !s || (P > 0 && (!params || !out))) return fail(DH_E_ARG, "null argument");
-    int rc = check_N(N);
-    if (rc) return rc;
-    if (P < 0) return fail(DH_E_ARG, "P < 0");
-    if (P == 0 || s->M == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    const size_t pb = (size_t)P * DH_PARAM_STRIDE * 8, ob = (size_t)P * s->M * 8;
-    HIP_TRY(ctx->params.reserve(pb));
-    HIP_TRY(ctx->out.reserve(ob));
-    HIP_TRY(hipMemcpyAsync(ctx->params.ptr, params, pb, hipMemcpyHostToDevice, ctx->stream));
-    rc = dh_surface_price_dev(ctx, s, (const double*)ctx->params.ptr, P, N, L,
-                              (double*)ctx->out.ptr, ctx->stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, ctx->out.ptr, ob, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return DH_OK;
-}
-
-int dh_surface_price_cols(dh_ctx* ctx, const dh_surface* s, const double* params,
-                          const double* spots, double r, int64_t P, int N, double L, double* out) {
-    if (!ctx || !s || (P > 0 && (!params || !spots || !out))) return fail(DH_E_ARG, "null argument");
-    int rc = check_N(N);
-    if (rc) return rc;
-    if (P < 0) return fail(DH_E_ARG, "P < 0");
-    if (P == 0 || s->M == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    hipStream_t st = ctx->stream;
-    const size_t ob = (size_t)P * s->M * 8;
-    HIP_TRY(ctx->params.reserve((size_t)P * DH_PARAM_STRIDE * 8));
-    HIP_TRY(ctx->aux0.reserve((size_t)P * 13 * 8));
-    HIP_TRY(ctx->aux1.reserve((size_t)P * 8));
-    HIP_TRY(ctx->out.reserve(ob));
-    HIP_TRY(hipMemcpyAsync(ctx->aux0.ptr, params, (size_t)P * 13 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->aux1.ptr, spots, (size_t)P * 8, hipMemcpyHostToDevice, st));
-    const int64_t n_el = P * DH_PARAM_STRIDE;
-    const int64_t nb = (n_el + 255) / 256;
-    if (nb > 0x7fffffffLL) return fail(DH_E_ARG, "launch too large");
-    hipLaunchKernelGGL(gen_records_kernel, dim3((unsigned)nb), dim3(256), 0, st,
-                       (const double*)ctx->aux0.ptr, (const double*)ctx->aux1.ptr, r, P,
-                       (double*)ctx->params.ptr);
-    HIP_TRY(hipGetLastError());
-    rc = dh_surface_price_dev(ctx, s, (const double*)ctx->params.ptr, P, N, L,
-                              (double*)ctx->out.ptr, st);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, ctx->out.ptr, ob, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DH_OK;
-}
-
-// A failed (un)registration is reported here and nowhere else: HIP's per-thread last error is
-// read back (cleared), so the next call's hipGetLastError check after a launch does not report it
-// (a caller that leaves an array pageable after a failed registration, _native.pinned, goes on)
-int dh_host_register(void* ptr, size_t bytes) {
-    if (!ptr || !bytes) return fail(DH_E_ARG, "null or empty range");
-    const hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterDefault);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DH_E_HIP, std::string("hipHostRegister: ") + hipGetErrorString(e));
-    }
-    return DH_OK;
-}
-
-int dh_host_unregister(void* ptr) {
-    if (!ptr) return fail(DH_E_ARG, "null argument");
-    const hipError_t e = hipHostUnregister(ptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DH_E_HIP, std::string("hipHostUnregister: ") + hipGetErrorString(e));
-    }
-    return DH_OK;
-}
-
-int dh_surface_loss(dh_ctx* ctx, const dh_surface* s, const double* params, int S, int N,
-                    double L, double* sse, int32_t* n_bad, double* prices) {
-    if (!ctx || !s || (S > 0 && (!params || !sse || !n_bad))) return fail(DH_E_ARG, "null argument");
-    int rc = check_N(N);
-    if (rc) return rc;
-    if (S < 0) return fail(DH_E_ARG, "S < 0");
-    if (S == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    const size_t pb = (size_t)S * DH_PARAM_STRIDE * 8;
-    double* d_prices = nullptr;
-    const size_t ob = (size_t)S * s->M * 8;
-    if (prices) {
-        HIP_TRY(ctx->out.reserve(ob));
-        d_prices = (double*)ctx->out.ptr;
-    }
-    if (S <= kZeroCopyMaxSets) {
-        // calibration-sized request: the kernels read the params and write sse / n_bad through
-        // pinned, mapped host memory -- one launch and one sync, no staging copies
-        HIP_TRY(ctx->h_params.reserve(pb));
-        HIP_TRY(ctx->h_loss.reserve((size_t)S * 12));
-        std::memcpy(ctx->h_params.ptr, params, pb);
-        double* h_sse = (double*)ctx->h_loss.ptr;
-        int32_t* h_bad = (int32_t*)(h_sse + S);
-        ctx->kp_src = (const double*)ctx->h_params.ptr;     // <= 14 records: in the arguments
-        ctx->kp_surf = s;
-        ctx->kp_n = S;
-        rc = dh_surface_loss_dev(ctx, s, (const double*)ctx->h_params.dptr, S, N, L,
-                                 (double*)ctx->h_loss.dptr, (int32_t*)((double*)ctx->h_loss.dptr + S),
-                                 d_prices, ctx->stream);
-        ctx->kp_src = nullptr;
-        ctx->kp_surf = nullptr;
-        ctx->kp_n = 0;
-        if (rc) return rc;
-        if (prices && s->M > 0)
-            HIP_TRY(hipMemcpyAsync(prices, d_prices, ob, hipMemcpyDeviceToHost, ctx->stream));
-        rc = spin_sync(ctx->stream);
-        if (rc) return rc;
-        std::memcpy(sse, h_sse, (size_t)S * 8);
-        std::memcpy(n_bad, h_bad, (size_t)S * 4);
-        return check_loss_counts(n_bad, S);
-    }
-    HIP_TRY(ctx->params.reserve(pb));
-    HIP_TRY(ctx->sse.reserve((size_t)S * 8));
-    HIP_TRY(ctx->bad.reserve((size_t)S * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->params.ptr, params, pb, hipMemcpyHostToDevice, ctx->stream));
-    rc = dh_surface_loss_dev(ctx, s, (const double*)ctx->params.ptr, S, N, L,
-                             (double*)ctx->sse.ptr, (int32_t*)ctx->bad.ptr, d_prices, ctx->stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(sse, ctx->sse.ptr, (size_t)S * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(n_bad, ctx->bad.ptr, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (prices && s->M > 0)
-        HIP_TRY(hipMemcpyAsync(prices, d_prices, ob, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return check_loss_counts(n_bad, S);
-}
-
-int dh_price_pairs(dh_ctx* ctx, const double* params, const double* K, const double* T,
-                   const int8_t* is_call, int64_t P, int N, double L, double* out) {
-    if (!ctx || (P > 0 && (!params || !K || !T || !is_call || !out)))
-        return fail(DH_E_ARG, "null argument");
-    int rc = check_N(N);
-    if (rc) return rc;
-    if (P < 0) return fail(DH_E_ARG, "P < 0");
-    if (P == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    const size_t pb = (size_t)P * DH_PARAM_STRIDE * 8, vb = (size_t)P * 8;
-    hipStream_t st = ctx->stream;
-    PriceArgs A{};
-    A.P = P;
-    double* d_out = nullptr;
-    const bool zc = P <= kZeroCopyMaxSets;
-    if (zc) {
-        // single options and small batches (DoubleHeston.pricing() calls): the kernel reads the
-        // inputs and writes the prices through pinned, mapped host memory -- one launch and one
-        // spin-wait instead of five staging copies, a read-back and a stream sync
-        const size_t need = pb + 3 * vb + (size_t)P * 4 + (size_t)P;
-        HIP_TRY(ctx->h_pairs.reserve(need));
-        char* h = (char*)ctx->h_pairs.ptr;
-        char* d = (char*)ctx->h_pairs.dptr;
-        std::memcpy(h, params, pb);
-        std::memcpy(h + pb, K, vb);
-        std::memcpy(h + pb + vb, T, vb);
-        int* perm = (int*)(h + pb + 3 * vb);
-        for (int64_t i = 0; i < P; ++i) perm[i] = (int)i;
-        std::memcpy(h + pb + 3 * vb + (size_t)P * 4, is_call, (size_t)P);
-        A.prm = (const double*)d;
-        A.K = (const double*)(d + pb);
-        A.T = (const double*)(d + pb + vb);
-        d_out = (double*)(d + pb + 2 * vb);
-        A.perm = (const int*)(d + pb + 3 * vb);
-        A.call = (const int8_t*)(d + pb + 3 * vb + (size_t)P * 4);
-    } else {
-        HIP_TRY(ctx->params.reserve(pb));
-        HIP_TRY(ctx->out.reserve(vb));
-        HIP_TRY(ctx->aux0.reserve(vb));
-        HIP_TRY(ctx->aux1.reserve(vb));
-        HIP_TRY(ctx->aux2.reserve((size_t)P));
-        HIP_TRY(ctx->aux3.reserve((size_t)P * 4));
-        std::vector<int> ident((size_t)P);
-        std::iota(ident.begin(), ident.end(), 0);
-        HIP_TRY(hipMemcpyAsync(ctx->params.ptr, params, pb, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ctx->aux0.ptr, K, vb, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ctx->aux1.ptr, T, vb, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ctx->aux2.ptr, is_call, (size_t)P, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ctx->aux3.ptr, ident.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));        // `ident` is pageable and leaves scope
-        A.prm = (const double*)ctx->params.ptr;
-        A.K = (const double*)ctx->aux0.ptr;
-        A.T = (const double*)ctx->aux1.ptr;
-        A.call = (const int8_t*)ctx->aux2.ptr;
-        A.perm = (const int*)ctx->aux3.ptr;
-        d_out = (double*)ctx->out.ptr;
-    }
-    A.paired = 1;
-    A.opt_cap = 2;
-    A.max_group = 1;
-    A.M = (int)P;
-    A.exact = per_term(ctx, N);
-    A.strike_mode = DH_STRIKE_ABSOLUTE;
-    A.N = N;
-    A.L = L;
-    A.out = d_out;
-    A.out_stride = 0;
-    rc = launch_price(ctx, A, st);
-    if (rc) return rc;
-    if (zc) {
-        rc = spin_sync(st);
-        if (rc) return rc;
-        std::memcpy(out, (char*)ctx->h_pairs.ptr + pb + 2 * vb, vb);
-        return DH_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(out, ctx->out.ptr, vb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DH_OK;
-}
-
-int dh_cf(dh_ctx* ctx, const double* params, const double* u, int n, double tau, double* re,
-          double* im) {
-    if (!ctx || !params || (n > 0 && (!u || !re || !im))) return fail(DH_E_ARG, "null argument");
-    if (n < 0) return fail(DH_E_ARG, "n < 0");
-    if (n == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    const size_t vb = (size_t)n * 8;
-    HIP_TRY(ctx->params.reserve(DH_PARAM_STRIDE * 8));
-    HIP_TRY(ctx->aux0.reserve(vb));
-    HIP_TRY(ctx->aux1.reserve(vb));
-    HIP_TRY(ctx->aux2.reserve(vb));
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(ctx->params.ptr, params, DH_PARAM_STRIDE * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->aux0.ptr, u, vb, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(cf_kernel, dim3((n + 255) / 256), dim3(256), 0, st,
-                       (const double*)ctx->params.ptr, (const double*)ctx->aux0.ptr, n, tau,
-                       (double*)ctx->aux1.ptr, (double*)ctx->aux2.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(re, ctx->aux1.ptr, vb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(im, ctx->aux2.ptr, vb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DH_OK;
-}
-
-int dh_cf_complex(dh_ctx* ctx, const double* params, const double* u_re, const double* u_im,
-                  int n, double tau, double* re, double* im) {
-    if (!ctx || !params || (n > 0 && (!u_re || !u_im || !re || !im)))
-        return fail(DH_E_ARG, "null argument");
-    if (n < 0) return fail(DH_E_ARG, "n < 0");
-    if (n == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    const size_t vb = (size_t)n * 8;
-    HIP_TRY(ctx->params.reserve(DH_PARAM_STRIDE * 8));
-    HIP_TRY(ctx->aux0.reserve(vb));
-    HIP_TRY(ctx->aux1.reserve(vb));
-    HIP_TRY(ctx->aux2.reserve(vb));
-    HIP_TRY(ctx->aux3.reserve(vb));
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(ctx->params.ptr, params, DH_PARAM_STRIDE * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->aux0.ptr, u_re, vb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->aux1.ptr, u_im, vb, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(cf_kernel_z, dim3((n + 255) / 256), dim3(256), 0, st,
-                       (const double*)ctx->params.ptr, (const double*)ctx->aux0.ptr,
-                       (const double*)ctx->aux1.ptr, n, tau, (double*)ctx->aux2.ptr,
-                       (double*)ctx->aux3.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(re, ctx->aux2.ptr, vb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(im, ctx->aux3.ptr, vb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DH_OK;
-}
-
-int dh_trunc_range(dh_ctx* ctx, const double* params, const double* K, const double* T,
-                   int64_t P, double L, double* a, double* b) {
-    if (!ctx || (P > 0 && (!params || !K || !T || !a || !b))) return fail(DH_E_ARG, "null argument");
-    if (P < 0) return fail(DH_E_ARG, "P < 0");
-    if (P == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    const size_t pb = (size_t)P * DH_PARAM_STRIDE * 8, vb = (size_t)P * 8;
-    HIP_TRY(ctx->params.reserve(pb));
-    HIP_TRY(ctx->aux0.reserve(vb));
-    HIP_TRY(ctx->aux1.reserve(vb));
-    HIP_TRY(ctx->aux2.reserve(vb));
-    HIP_TRY(ctx->aux3.reserve(vb));
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(ctx->params.ptr, params, pb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->aux0.ptr, K, vb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->aux1.ptr, T, vb, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(trunc_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st,
-                       (const double*)ctx->params.ptr, (const double*)ctx->aux0.ptr,
-                       (const double*)ctx->aux1.ptr, P, L, (double*)ctx->aux2.ptr,
-                       (double*)ctx->aux3.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(a, ctx->aux2.ptr, vb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(b, ctx->aux3.ptr, vb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DH_OK;
-}
-
-int dh_cos_coeffs(dh_ctx* ctx, const int32_t* k, int n, double c, double d, double a, double b,
-                  double* chi, double* psi) {
-    if (!ctx || (n > 0 && (!k || !chi || !psi))) return fail(DH_E_ARG, "null argument");
-    if (n < 0) return fail(DH_E_ARG, "n < 0");
-    if (n == 0) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    const size_t vb = (size_t)n * 8;
-    HIP_TRY(ctx->aux0.reserve((size_t)n * 4));
-    HIP_TRY(ctx->aux1.reserve(vb));
-    HIP_TRY(ctx->aux2.reserve(vb));
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(ctx->aux0.ptr, k, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(coeff_kernel, dim3((n + 255) / 256), dim3(256), 0, st,
-                       (const int32_t*)ctx->aux0.ptr, n, c, d, a, b, (double*)ctx->aux1.ptr,
-                       (double*)ctx->aux2.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(chi, ctx->aux1.ptr, vb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(psi, ctx->aux2.ptr, vb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DH_OK;
-}
-
-}  // extern "C"
-
-// ----------------------------------------------------------------------------------------------
-// device-resident multi-start L-BFGS-B (dh_calibrate_lbfgs): what the driver (dh_lb_driver.h,
-// included at the end) shares with the one-shot entry points below
-// ----------------------------------------------------------------------------------------------
-// Nothing below is contracted into FMAs: the step kernel must compute the bits of the CPU build
-// of dh_lbfgs.h (tests/native/lb_host.cpp).
+// Nothing below, the headers included, is contracted into FMAs: the device L-BFGS-B (dh_lbfgs.h,
+// dh_lb_driver.h) must compute the bits of its CPU build (tests/native/lb_host.cpp), and the
+// feature headers the bits their tests pin.  Device code above this line is contracted.
 #pragma clang fp contract(off)
 
 namespace {
@@ -4092,13 +2722,6 @@ __device__ __forceinline__ double lb_transform(int i, double x) {
     if (i == 11) return x;
     return exp(x);
 }
-
-}  // namespace
-
-// ----------------------------------------------------------------------------------------------
-// one-shot entry points in the shape SURVEY.md 8(b) proposes (a surface per call)
-// ----------------------------------------------------------------------------------------------
-namespace {
 
 // unconstrained x [S][13] -> param records (exp / tanh / identity, lbfgs_calibrator.py:62-87)
 // and Feller penalties (:113-116); one thread per set, the expressions of lb_emit
@@ -4131,467 +2754,16 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
 
 }  // namespace
 
-extern "C" int dh_price_batch(dh_ctx* ctx, const double* params, int64_t P, const double* K,
-                              const double* T, const int8_t* is_call, int M, int N, double L,
-                              double* out) {
-    if (!ctx || (P > 0 && M > 0 && (!params || !out))) return fail(DH_E_ARG, "null argument");
-    if (P < 0) return fail(DH_E_ARG, "P < 0");
-    dh_surface* s = nullptr;
-    int rc = dh_surface_create(ctx, K, T, is_call, nullptr, M, DH_STRIKE_ABSOLUTE, &s);
-    if (rc) return rc;
-    rc = dh_surface_price(ctx, s, params, P, N, L, out);
-    dh_surface_destroy(s);
-    return rc;
-}
-
-extern "C" int dh_loss_batch(dh_ctx* ctx, const double* x, int S, const double* K, const double* T,
-                             const int8_t* is_call, const double* mkt, int M, double S0, double r,
-                             int N, double L, double* loss, int32_t* n_invalid) {
-    if (!ctx || (S > 0 && (!x || !loss || !n_invalid))) return fail(DH_E_ARG, "null argument");
-    if (S < 0) return fail(DH_E_ARG, "S < 0");
-    if (M > 0 && !mkt) return fail(DH_E_ARG, "mkt is null");
-    int rc = check_N(N);
-    if (rc) return rc;
-    if (S == 0) return DH_OK;
-    if (M == 0) {                                   // np.mean([]) -> nan (lbfgs_calibrator.py:163)
-        for (int i = 0; i < S; ++i) {
-            loss[i] = __builtin_nan("");
-            n_invalid[i] = 0;
-        }
-        return DH_OK;
-    }
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    dh_surface* s = nullptr;
-    rc = dh_surface_create(ctx, K, T, is_call, mkt, M, DH_STRIKE_ABSOLUTE, &s);
-    if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const size_t xb = (size_t)S * dhlb::kN * 8;
-    auto run = [&]() -> int {
-        HIP_TRY(ctx->aux0.reserve(xb));
-        HIP_TRY(ctx->aux1.reserve((size_t)S * DH_PARAM_STRIDE * 8));
-        HIP_TRY(ctx->aux2.reserve((size_t)S * 8 * 3));     // pen | sse | loss
-        HIP_TRY(ctx->aux3.reserve((size_t)S * 4));
-        double* d_x = (double*)ctx->aux0.ptr;
-        double* d_rec = (double*)ctx->aux1.ptr;
-        double* d_pen = (double*)ctx->aux2.ptr;
-        double* d_sse = d_pen + S;
-        double* d_loss = d_sse + S;
-        int* d_bad = (int*)ctx->aux3.ptr;
-        HIP_TRY(hipMemcpyAsync(d_x, x, xb, hipMemcpyHostToDevice, st));
-        const unsigned b = (unsigned)((S + 255) / 256);
-        hipLaunchKernelGGL(x_records_kernel, dim3(b), dim3(256), 0, st, d_x, S, S0, r, d_rec, d_pen);
-        HIP_TRY(hipGetLastError());
-        int e = surface_loss_launch(ctx, s, d_rec, S, N, L, d_sse, (int32_t*)d_bad, nullptr, st,
-                                    nullptr);
-        if (e) return e;
-        hipLaunchKernelGGL(loss_finalize_kernel, dim3(b), dim3(256), 0, st, d_sse, d_bad, d_pen, S,
-                           s->M, d_loss);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(loss, d_loss, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(n_invalid, d_bad, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return DH_OK;
-    };
-    rc = run();
-    dh_surface_destroy(s);
-    return rc;
-}
-
-// ----------------------------------------------------------------------------------------------
-// function + FD-gradient requests for the host (SciPy) driver
-// ----------------------------------------------------------------------------------------------
-namespace {
-
-// The request's points (scipy/optimize/_numdiff.py:498-511: x0, then x0 + h_i e_i with h = 1e-8,
-// or sqrt(eps) sign(x) max(1, |x|) where the absolute step vanishes), their model params (exp /
-// tanh / identity, lbfgs_calibrator.py:62-87) and Feller penalties (:113-116): rec [S * 14][16],
-// pen [S * 14], dx [S][13].  The caller passes the model params of x0 and x0 + h (model:
-// [2][S][13]) when they must be the bits of its own exp / tanh (NumPy's, as the reference's
-// transform_params); otherwise they come from libm here.
-void fg_points(const double* x0, const double* model, int S, double S0, double r, double* rec,
-               double* pen, double* dx) {
-    constexpr int kP = dhlb::kPts, kN = dhlb::kN;
-    for (int st = 0; st < S; ++st) {
-        const double* x = x0 + (size_t)st * kN;
-        double pb[kN], pp[kN];
-        for (int i = 0; i < kN; ++i) {
-            double h = kFdStep;
-            if ((x[i] + h) - x[i] == 0.0)
-                h = kSqrtEps * (x[i] >= 0.0 ? 1.0 : -1.0) * std::max(1.0, std::fabs(x[i]));
-            const double xh = x[i] + h;
-            dx[(size_t)st * kN + i] = xh - x[i];
-            if (model) {
-                pb[i] = model[(size_t)st * kN + i];
-                pp[i] = model[((size_t)S + st) * kN + i];
-            } else {
-                const bool th = i == 4 || i == 9, id = i == 11;
-                pb[i] = th ? std::tanh(x[i]) : (id ? x[i] : std::exp(x[i]));
-                pp[i] = th ? std::tanh(xh) : (id ? xh : std::exp(xh));
-            }
-        }
-        for (int t = 0; t < kP; ++t) {
-            double* o = rec + ((size_t)st * kP + t) * DH_PARAM_STRIDE;
-            for (int i = 0; i < kN; ++i) o[i] = (i == t - 1) ? pp[i] : pb[i];
-            const double v1 = o[3] * o[3] - 2.0 * o[1] * o[2];
-            const double v2 = o[8] * o[8] - 2.0 * o[6] * o[7];
-            pen[(size_t)st * kP + t] = 1000.0 * ((v1 > 0.0 ? v1 : 0.0) + (v2 > 0.0 ? v2 : 0.0));
-            o[13] = S0;
-            o[14] = r;
-            o[15] = 0.0;
-        }
-    }
-}
-
-// loss = n_bad ? 1e10 : sse / M + Feller (lbfgs_calibrator.py:152-166); f, the FD gradient
-// (f_i - f_0) / dx_i as SciPy forms it, and the smallest valid loss of the request
-void fg_finish(int S, int M, const double* sse, const int32_t* bad, const double* pen,
-               const double* dx, double* f, double* g, double* low) {
-    constexpr int kP = dhlb::kPts, kN = dhlb::kN;
-    for (int st = 0; st < S; ++st) {
-        double lo = __builtin_huge_val(), fl[kP];
-        for (int t = 0; t < kP; ++t) {
-            const size_t i = (size_t)st * kP + t;
-            fl[t] = bad[i] > 0 ? kInvalidLoss : sse[i] / (double)M + pen[i];
-            if (fl[t] == fl[t] && fl[t] != kInvalidLoss && fl[t] < lo) lo = fl[t];
-        }
-        f[st] = fl[0];
-        low[st] = lo;
-        for (int i = 0; i < kN; ++i)
-            g[(size_t)st * kN + i] = (fl[i + 1] - fl[0]) / dx[(size_t)st * kN + i];
-    }
-}
-
-int fg_check(dh_ctx* ctx, const dh_surface* s, int S) {
-    if (!s->has_mkt) return fail(DH_E_ARG, "surface has no market prices");
-    if (s->M == 0) return fail(DH_E_ARG, "empty market (the loss is NaN)");
-    if (S < 0) return fail(DH_E_ARG, "S < 0");
-    (void)ctx;
-    return DH_OK;
-}
-
-}  // namespace
-
-extern "C" int dh_surface_fg(dh_ctx* ctx, const dh_surface* s, const double* x0,
-                             const double* model, int S, double S0, double r, int N, double L,
-                             double* f, double* g, double* low) {
-    if (!ctx || !s || (S > 0 && (!x0 || !f || !g || !low))) return fail(DH_E_ARG, "null argument");
-    int rc = fg_check(ctx, s, S);
-    if (rc) return rc;
-    if (S == 0) return DH_OK;
-    const size_t P = (size_t)S * dhlb::kPts;
-    std::vector<double> rec(P * DH_PARAM_STRIDE), pen(P), dx((size_t)S * dhlb::kN), sse(P);
-    std::vector<int32_t> bad(P);
-    fg_points(x0, model, S, S0, r, rec.data(), pen.data(), dx.data());
-    rc = dh_surface_loss(ctx, s, rec.data(), (int)P, N, L, sse.data(), bad.data(), nullptr);
-    if (rc) return rc;
-    fg_finish(S, s->M, sse.data(), bad.data(), pen.data(), dx.data(), f, g, low);
-    return DH_OK;
-}
-
-extern "C" int dh_surface_fg_begin(dh_ctx* ctx, const dh_surface* s, const double* x0,
-                                   const double* model, int S, double S0, double r, int N,
-                                   double L, int slot) {
-    if (!ctx || !s || (S > 0 && !x0)) return fail(DH_E_ARG, "null argument");
-    if (slot < 0 || slot >= DH_FG_SLOTS) return fail(DH_E_ARG, "slot out of range");
-    int rc = fg_check(ctx, s, S);
-    if (rc) return rc;
-    rc = check_N(N);
-    if (rc) return rc;
-    if (s->ctx && s->ctx->device != ctx->device)
-        return fail(DH_E_ARG, "surface and context are on different devices");
-    auto& F = ctx->fg[slot];
-    if (F.pending) return fail(DH_E_ARG, "slot has a request in flight (call dh_surface_fg_end)");
-    const size_t P = (size_t)S * dhlb::kPts;
-    if (P > (size_t)kZeroCopyMaxSets)
-        return fail(DH_E_ARG, "too many starts for one asynchronous request (use dh_surface_fg)");
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    // The loss launch may grow the context's device scratch (partials, counters, the prologue
-    // buffer, table / clamp workspaces), whose sizes follow from the surface, N and the param-set
-    // count only.  A grow frees buffers the other slot's enqueued launch still reads.  hipFree
-    // happens to synchronise the device first, but nothing here relies on that: wait for the
-    // other slots (their requests share the stream) whenever this request is not covered by an
-    // earlier one on the same surface and N (the pipelined SciPy driver's requests always are,
-    // after its first round).
-    const size_t units = P * (size_t)std::max(s->n_tiles, s->n_groups);
-    const bool covered = s == ctx->fg_surf && N == ctx->fg_N && units <= ctx->fg_max_units;
-    bool others = false;
-    for (int o = 0; o < DH_FG_SLOTS; ++o) others = others || (o != slot && ctx->fg[o].pending);
-    if (others && !covered) HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (s != ctx->fg_surf || N != ctx->fg_N) {
-        ctx->fg_surf = s;
-        ctx->fg_N = N;
-        ctx->fg_max_units = 0;
-    }
-    ctx->fg_max_units = std::max(ctx->fg_max_units, units);
-    HIP_TRY(F.h_params.reserve(P * DH_PARAM_STRIDE * 8));
-    HIP_TRY(F.h_loss.reserve(P * 12));
-    F.pen.resize(P);
-    F.dx.resize((size_t)S * dhlb::kN);
-    if (!F.done) HIP_TRY(hipEventCreateWithFlags(&F.done, hipEventDisableTiming));
-    F.S = S;
-    F.M = s->M;
-    F.surf = s;
-    if (S == 0) {
-        HIP_TRY(hipEventRecord(F.done, ctx->stream));
-        F.pending = true;
-        return DH_OK;
-    }
-    fg_points(x0, model, S, S0, r, (double*)F.h_params.ptr, F.pen.data(), F.dx.data());
-    // the records also travel in the fused launch's kernel arguments when they fit (KargParams)
-    ctx->kp_src = (const double*)F.h_params.ptr;
-    ctx->kp_surf = s;
-    ctx->kp_n = (int64_t)P;
-    ctx->kp_done = F.done;
-    ctx->kp_done_set = false;
-    rc = dh_surface_loss_dev(ctx, s, (const double*)F.h_params.dptr, (int)P, N, L,
-                             (double*)F.h_loss.dptr, (int32_t*)((double*)F.h_loss.dptr + P),
-                             nullptr, ctx->stream);
-    ctx->kp_src = nullptr;
-    ctx->kp_surf = nullptr;
-    ctx->kp_n = 0;
-    ctx->kp_done = nullptr;
-    if (rc) return rc;
-    if (!ctx->kp_done_set) HIP_TRY(hipEventRecord(F.done, ctx->stream));
-    ctx->kp_done_set = false;
-    F.pending = true;
-    return DH_OK;
-}
-
-extern "C" int dh_surface_fg_end(dh_ctx* ctx, const dh_surface* s, int slot, int S, double* f,
-                                 double* g, double* low) {
-    if (!ctx || !s) return fail(DH_E_ARG, "null argument");
-    if (slot < 0 || slot >= DH_FG_SLOTS) return fail(DH_E_ARG, "slot out of range");
-    auto& F = ctx->fg[slot];
-    if (!F.pending) return fail(DH_E_ARG, "no request in flight in this slot");
-    // the slot belongs to the context: the caller must name the request it enqueued (its surface
-    // and start count, which size f / g / low), else its buffers may be smaller than F.S rows
-    if (s != F.surf) return fail(DH_E_ARG, "slot's request was enqueued on another surface");
-    if (S != F.S)
-        return fail(DH_E_ARG, "slot's request has " + std::to_string(F.S) + " starts, caller passed " +
-                                  std::to_string(S));
-    if (F.S > 0 && (!f || !g || !low)) return fail(DH_E_ARG, "null argument");
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    const size_t P = (size_t)F.S * dhlb::kPts;
-    for (;;) {                          // busy-wait: an optimizer iteration waits on it
-        const hipError_t e = hipEventQuery(F.done);
-        if (e == hipSuccess) break;
-        if (e != hipErrorNotReady) {
-            F.pending = false;
-            return fail(DH_E_HIP, std::string("hipEventQuery: ") + hipGetErrorString(e));
-        }
-    }
-    F.pending = false;
-    const int32_t* nb = (const int32_t*)((double*)F.h_loss.ptr + P);
-    const int crc = check_loss_counts(nb, (int64_t)P);
-    if (crc) return crc;
-    fg_finish(F.S, F.M, (const double*)F.h_loss.ptr, nb, F.pen.data(), F.dx.data(), f, g, low);
-    return DH_OK;
-}
-
-extern "C" int dh_surface_fg_cancel(dh_ctx* ctx, int slot) {
-    if (!ctx) return fail(DH_E_ARG, "null argument");
-    if (slot < 0 || slot >= DH_FG_SLOTS) return fail(DH_E_ARG, "slot out of range");
-    auto& F = ctx->fg[slot];
-    if (!F.pending) return DH_OK;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    F.pending = false;                  // cleared even if the wait fails: the slot is usable again
-    HIP_TRY(hipEventSynchronize(F.done));
-    return DH_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// multi-GPU: an RCCL communicator for callers without torch.distributed (SURVEY 8(b)'s
-// dh_allgather_best, 8(e) multi-start sharding).  librccl.so.1 is resolved at run time: with
-// torch imported that is torch's own copy (the same soname), otherwise ROCm's, so a process holds
-// one RCCL either way and the library does not link it.
-// ----------------------------------------------------------------------------------------------
-namespace {
-
-struct RcclApi {
-    bool ok = false;
-    std::string err;
-    ncclResult_t (*get_unique_id)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*comm_init_rank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*all_gather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t,
-                               hipStream_t) = nullptr;
-    ncclResult_t (*broadcast)(const void*, void*, size_t, ncclDataType_t, int, ncclComm_t,
-                              hipStream_t) = nullptr;
-    ncclResult_t (*comm_destroy)(ncclComm_t) = nullptr;
-    const char* (*error_string)(ncclResult_t) = nullptr;
-};
-
-const RcclApi& rccl() {
-    static const RcclApi api = [] {
-        RcclApi a;
-        void* h = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-        if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-        if (!h) {
-            const char* e = dlerror();
-            a.err = std::string("librccl not found: ") + (e ? e : "");
-            return a;
-        }
-        auto sym = [&](auto& fn, const char* name) {
-            fn = reinterpret_cast<std::remove_reference_t<decltype(fn)>>(dlsym(h, name));
-            if (!fn && a.err.empty()) a.err = std::string("librccl lacks ") + name;
-        };
-        sym(a.get_unique_id, "ncclGetUniqueId");
-        sym(a.comm_init_rank, "ncclCommInitRank");
-        sym(a.all_gather, "ncclAllGather");
-        sym(a.broadcast, "ncclBroadcast");
-        sym(a.comm_destroy, "ncclCommDestroy");
-        sym(a.error_string, "ncclGetErrorString");
-        a.ok = a.err.empty();
-        return a;
-    }();
-    return api;
-}
-
-int nccl_fail(const char* what, ncclResult_t r) {
-    return fail(DH_E_COMM, std::string(what) + ": " + rccl().error_string(r));
-}
-
-#define NCCL_TRY(expr)                                       \
-    do {                                                     \
-        const ncclResult_t _r = (expr);                      \
-        if (_r != ncclSuccess) return nccl_fail(#expr, _r);  \
-    } while (0)
-
-}  // namespace
-
-struct dh_comm {
-    dh_ctx* ctx = nullptr;
-    ncclComm_t comm = nullptr;
-    int world = 0, rank = 0;
-    DevBuf send, recv;
-};
-
-extern "C" int dh_comm_id(unsigned char* id) {
-    if (!id) return fail(DH_E_ARG, "id is null");
-    const RcclApi& R = rccl();
-    if (!R.ok) return fail(DH_E_COMM, R.err);
-    ncclUniqueId u;
-    NCCL_TRY(R.get_unique_id(&u));
-    static_assert(sizeof(u) == DH_COMM_ID_BYTES, "ncclUniqueId size");
-    std::memcpy(id, &u, sizeof(u));
-    return DH_OK;
-}
-
-extern "C" int dh_comm_create(dh_ctx* ctx, const unsigned char* id, int world, int rank,
-                              dh_comm** out) {
-    if (!ctx || !id || !out) return fail(DH_E_ARG, "null argument");
-    *out = nullptr;
-    if (world < 1 || rank < 0 || rank >= world) return fail(DH_E_ARG, "rank / world out of range");
-    const RcclApi& R = rccl();
-    if (!R.ok) return fail(DH_E_COMM, R.err);
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    ncclUniqueId u;
-    std::memcpy(&u, id, sizeof(u));
-    dh_comm* c = new (std::nothrow) dh_comm();
-    if (!c) return fail(DH_E_ALLOC, "comm alloc");
-    const ncclResult_t r = R.comm_init_rank(&c->comm, world, u, rank);   // joins every rank
-    if (r != ncclSuccess) {
-        delete c;
-        return nccl_fail("ncclCommInitRank", r);
-    }
-    c->ctx = ctx;
-    c->world = world;
-    c->rank = rank;
-    *out = c;
-    return DH_OK;
-}
-
-extern "C" int dh_comm_destroy(dh_comm* c) {
-    if (!c) return DH_OK;
-    int rc = DH_OK;
-    {
-        DeviceScope dev_scope(c->ctx->device);
-        if (c->comm) {
-            const ncclResult_t r = rccl().comm_destroy(c->comm);
-            if (r != ncclSuccess) rc = nccl_fail("ncclCommDestroy", r);
-        }
-        c->send.release();
-        c->recv.release();
-    }
-    delete c;
-    return rc;
-}
-
-extern "C" int dh_comm_broadcast(dh_comm* c, double* buf, int64_t n, int root) {
-    if (!c || (n > 0 && !buf)) return fail(DH_E_ARG, "null argument");
-    if (root < 0 || root >= c->world) return fail(DH_E_ARG, "root out of range");
-    if (n <= 0) return DH_OK;
-    DeviceScope dev_scope(c->ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    const size_t bytes = (size_t)n * sizeof(double);
-    hipStream_t st = c->ctx->stream;
-    HIP_TRY(c->send.reserve(bytes));
-    if (c->rank == root) HIP_TRY(hipMemcpyAsync(c->send.ptr, buf, bytes, hipMemcpyHostToDevice, st));
-    NCCL_TRY(rccl().broadcast(c->send.ptr, c->send.ptr, (size_t)n, ncclFloat64, root, c->comm, st));
-    HIP_TRY(hipMemcpyAsync(buf, c->send.ptr, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DH_OK;
-}
-
-extern "C" int dh_comm_allgather(dh_comm* c, const double* send, int64_t n, double* recv) {
-    if (!c || (n > 0 && (!send || !recv))) return fail(DH_E_ARG, "null argument");
-    if (n < 0) return fail(DH_E_ARG, "n < 0");
-    if (n == 0) return DH_OK;
-    DeviceScope dev_scope(c->ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    hipStream_t st = c->ctx->stream;
-    const size_t bytes = (size_t)n * sizeof(double);
-    HIP_TRY(c->send.reserve(bytes));
-    HIP_TRY(c->recv.reserve(bytes * c->world));
-    HIP_TRY(hipMemcpyAsync(c->send.ptr, send, bytes, hipMemcpyHostToDevice, st));
-    NCCL_TRY(rccl().all_gather(c->send.ptr, c->recv.ptr, (size_t)n, ncclFloat64, c->comm, st));
-    HIP_TRY(hipMemcpyAsync(recv, c->recv.ptr, bytes * c->world, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DH_OK;
-}
-
-extern "C" int dh_best_start(const double* all, int64_t rows, int width, int col_start,
-                             int col_fun, int* best) {
-    if (!best || (rows > 0 && !all)) return fail(DH_E_ARG, "null argument");
-    if (width < 1 || col_start < 0 || col_start >= width || col_fun < 0 || col_fun >= width)
-        return fail(DH_E_ARG, "column out of range");
-    // lbfgs_calibrator.py:271-275: starts in order, best_loss = inf, strict < (NaN never wins);
-    // rows with a negative start index are padding
-    std::vector<std::pair<double, double>> by_start;           // (start, fun)
-    by_start.reserve((size_t)std::max<int64_t>(rows, 0));
-    for (int64_t i = 0; i < rows; ++i) {
-        const double s = all[i * width + col_start];
-        if (s >= 0.0) by_start.emplace_back(s, all[i * width + col_fun]);
-    }
-    std::stable_sort(by_start.begin(), by_start.end(),
-                     [](const auto& a, const auto& b) { return a.first < b.first; });
-    double best_loss = __builtin_huge_val();
-    *best = -1;
-    for (const auto& e : by_start)
-        if (e.second < best_loss) {
-            best_loss = e.second;
-            *best = (int)e.first;
-        }
-    return DH_OK;
-}
-
-extern "C" int dh_allgather_best(dh_comm* c, const double* rec, int rows, int width,
-                                 int col_start, int col_fun, double* all, int* best) {
-    if (!c || !all || !best || (rows > 0 && !rec)) return fail(DH_E_ARG, "null argument");
-    if (rows < 0 || width < 1) return fail(DH_E_ARG, "rows / width out of range");
-    const int rc = dh_comm_allgather(c, rec, (int64_t)rows * width, all);
-    if (rc) return rc;
-    return dh_best_start(all, (int64_t)rows * c->world, width, col_start, col_fun, best);
-}
-
-#include "dh_gen_device.h"
-#include "dh_iv.h"
-#include "dh_iv_loss.h"
-#include "dh_loss_rows.h"
-#include "dh_lb_driver.h"
-#include "dh_math_probe.h"
-#include "dh_mc.h"
+// The host side and the features, in this one translation unit.  Each header needs the kernels
+// above and the headers named after it here.
+#include "dh_host.h"         // errors, buffers, dh_ctx / dh_surface, DeviceScope, checks: none
+#include "dh_launch.h"       // the table of kernel builds, the launch planner: dh_host.h
+#include "dh_api.h"          // context, surface, price, loss, function+gradient calls: dh_launch.h
+#include "dh_comm.h"         // the RCCL communicator: dh_host.h
+#include "dh_gen_device.h"   // the generator's device draw (defines GenBufs): dh_api.h
+#include "dh_iv.h"           // implied vols: dh_api.h
+#include "dh_iv_loss.h"      // the vol-space loss stages: dh_iv.h, dh_api.h
+#include "dh_loss_rows.h"    // per-set market rows: dh_iv_loss.h
+#include "dh_lb_driver.h"    // the device-resident L-BFGS-B: dh_api.h, dh_iv_loss.h, dh_loss_rows.h
+#include "dh_math_probe.h"   // the device math primitives one by one: dh_host.h
+#include "dh_mc.h"           // the Monte Carlo path pricer: dh_host.h

@@ -671,6 +671,30 @@ def test_fg_begin_single_start_records_in_kernel_arguments(dh, calib_golden, N):
             os.environ["DHCOS_KARG_PARAMS"] = old
 
 
+@pytest.mark.parametrize("N", [64, 256])
+def test_fg_begin_single_start_equals_per_point_losses_bitwise(dh, calib_golden, N):
+    """A one-start asynchronous request (14 records in the fused launch's kernel arguments) at the
+    fused kernel's 64- and 256-thread table widths, on a surface of 32 maturities: f, g and low
+    are the bits of the same 14 points through loss_terms (fg_from_losses), fused and split."""
+    from dhcos import _native
+    from dhcos.calibrator import fd_models, fg_from_losses
+    params, _, K, T, call = _surface_case(53, P=1, M=96, n_T=32, N=N)
+    T[:32] = np.linspace(0.1, 2.0, 32)                  # every one of the 32 maturities
+    mkt = O.price_many(params[0], 100.0, K, T, 0.03, call, N) * (1 + 0.02 * np.cos(np.arange(96.0)))
+    market = [{"strike": k, "maturity": t, "price": float(p), "option_type": "call" if c else "put"}
+              for k, t, p, c in zip(K, T, mkt, call)]
+    cal = dh.DoubleHestonJumpCalibrator(100.0, 0.03, market, N=N)
+    surf = cal._get_surface()
+    x0 = np.array([calib_golden["fd_guess0"]["x0"]], dtype=float)
+    surf.fg_begin(x0, 100.0, 0.03, N, model=fd_models(x0), slot=0)
+    got = surf.fg_end(0)
+    assert surf.ctx.last_path == _native.PATH_FUSED
+    for path in (_native.PATH_AUTO, _native.PATH_SPLIT):
+        want = _with_path(surf.ctx, path, lambda: fg_from_losses(cal, x0))
+        for u, v in zip(got, want):
+            assert np.array_equal(u, v)
+
+
 def test_characteristic_function_complex_phi(dh, cf_complex_golden):
     """DoubleHeston.characteristic_function at complex phi (double_heston.py:48-61 documents
     phi : complex) against the reference's values: 216 scalar points (damped shifts u - i alpha,
@@ -1106,11 +1130,25 @@ def test_fused_equals_split_bitwise(dh, seed, P, M, n_T, N):
     value by the same expressions in the same order: prices, loss sums and invalid counts are
     identical word for word (calls and puts, clamp-widened strikes, price and loss modes), and
     both match the oracle."""
-    from dhcos import _native
     params, rec, K, T, call = _surface_case(seed, P=P, M=M, n_T=n_T, N=N)
     if M >= 40:
         K[:4] = [3.0, 30.0, 400.0, 5000.0]                    # clamp-widened at short maturities
         T[:4] = T.min()
+    _check_fused_equals_split(params, rec, K, T, call, N)
+
+
+@pytest.mark.parametrize("N", [64, 100])
+def test_fused_wide_build_equals_split_bitwise(dh, N):
+    """The same equalities for the fused kernel's 5-wave build at its 64- and 128-thread table
+    widths (N = 64, 100): 128 param sets x 32 one-option maturity groups, a grid of 4,096 blocks
+    (the parameters above reach that build at N = 256 alone)."""
+    params, rec, K, _, call = _surface_case(52, P=128, M=32, n_T=32, N=N)
+    _check_fused_equals_split(params, rec, K, np.linspace(0.1, 2.0, 32), call, N)
+
+
+def _check_fused_equals_split(params, rec, K, T, call, N):
+    from dhcos import _native
+    P = rec.shape[0]
     ctx = _native.default_context()
     mkt = np.abs(O.price_many(params[0], 100.0, K, T, 0.03, call, N)) + 1e-3
     surf = _native.Surface(ctx, K, T, call, mkt)
