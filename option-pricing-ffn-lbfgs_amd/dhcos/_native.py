@@ -21,18 +21,26 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DHCOS_LIB", os.path.join(_HERE, "libdhcos.so"))
 
+# the header's sizes and enums (tests/test_native_abi.py holds them to include/dhcos.h)
 PARAM_STRIDE = 16
 MAX_N = 2048                   # longest series of the table (fast) path (DH_MAX_N)
 MAX_N_PER_TERM = 65536         # longest accepted; longer than MAX_N runs the per-term path
 STRIKE_ABSOLUTE = 0
 STRIKE_PCT_SPOT = 1
-FG_SLOTS = 4                   # request slots of dh_surface_fg_begin / _end (DH_FG_SLOTS)
 PATH_AUTO, PATH_SPLIT, PATH_FUSED, PATH_GEN = 0, 1, 2, 3   # PATH_GEN: reported only (AUTO)
+FG_SLOTS = 4                   # request slots of dh_surface_fg_begin / _end (DH_FG_SLOTS)
+GEN_LOC_WORDS = 627            # DH_GEN_LOC_WORDS: key[624], pos, has_gauss, cached gauss
+COMM_ID_BYTES = 128
+MC_KINDS = {"european": 0, "asian": 1, "up_and_out": 2, "down_and_out": 3}   # DH_MC_*
+MC_MAX_OPTIONS = 64            # DH_MC_MAX_OPTIONS
+MC_POISSON_CAP = 16            # DH_MC_POISSON_CAP
 STAMPS_PER_BLOCK = 32          # kStamps of the DH_STAMPS build (csrc/dh_kernels.hip)
 
 _dp = C.POINTER(C.c_double)
 _i8p = C.POINTER(C.c_int8)
 _i32p = C.POINTER(C.c_int32)
+_i64p = C.POINTER(C.c_int64)
+_u32p = C.POINTER(C.c_uint32)
 _vp = C.c_void_p
 
 
@@ -49,127 +57,121 @@ class LbResult(C.Structure):
                 ("task", C.c_int32), ("warnflag", C.c_int32), ("n_calls", C.c_int32),
                 ("pad", C.c_int32)]
 
+
 class McOption(C.Structure):
     """dh_mc_option (include/dhcos.h): one option of the Monte Carlo pricer."""
     _fields_ = [("kind", C.c_int32), ("is_call", C.c_int32), ("strike", C.c_double),
                 ("maturity", C.c_double), ("barrier", C.c_double)]
 
 
-MC_KINDS = {"european": 0, "asian": 1, "up_and_out": 2, "down_and_out": 3}   # DH_MC_*
-MC_MAX_OPTIONS = 64            # DH_MC_MAX_OPTIONS
-MC_POISSON_CAP = 16            # DH_MC_POISSON_CAP
+_int, _i64, _dbl = C.c_int, C.c_int64, C.c_double          # the header's int, int64_t, double
+_lbo, _lbr, _mco = C.POINTER(LbOptions), C.POINTER(LbResult), C.POINTER(McOption)
 
-# name -> (restype, argtypes); mirrors include/dhcos.h one to one
+# name -> (restype, argtypes); mirrors include/dhcos.h one to one, in its order
 SIGNATURES = {
-    "dh_mc_price": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(McOption), C.c_int, C.c_int64,
-                              C.c_int, C.c_uint64, _vp, _vp]),
-    "dh_mc_price_dev": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(McOption), C.c_int, C.c_int64,
-                                  C.c_int, C.c_uint64, _vp, _vp, _vp]),
-    "dh_mc_paths": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int64, C.c_int,
-                              C.c_uint64, _vp]),
-    "dh_version": (C.c_int, []),
+    # ---- context
+    "dh_version": (_int, []),
     "dh_last_error": (C.c_char_p, []),
-    "dh_device_count": (C.c_int, [_i32p]),
-    "dh_ctx_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
-    "dh_ctx_destroy": (C.c_int, [_vp]),
-    "dh_ctx_synchronize": (C.c_int, [_vp]),
+    "dh_device_count": (_int, [_i32p]),
+    "dh_ctx_create": (_int, [_int, C.POINTER(_vp)]),
+    "dh_ctx_destroy": (_int, [_vp]),
+    "dh_ctx_synchronize": (_int, [_vp]),
     "dh_ctx_stream": (_vp, [_vp]),
-    "dh_ctx_set_exact": (C.c_int, [_vp, C.c_int]),
-    "dh_ctx_set_tail_cut": (C.c_int, [_vp, C.c_int]),
-    "dh_ctx_set_path": (C.c_int, [_vp, C.c_int]),
-    "dh_ctx_last_path": (C.c_int, [_vp]),
-    "dh_ctx_debug_stamps": (C.c_int, [_vp, C.c_int]),
-    "dh_ctx_read_stamps": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int64,
-                                     C.POINTER(C.c_int64)]),
-    "dh_surface_create": (C.c_int, [_vp, _dp, _dp, _i8p, _dp, C.c_int, C.c_int, C.POINTER(_vp)]),
-    "dh_surface_destroy": (C.c_int, [_vp]),
-    "dh_surface_size": (C.c_int, [_vp, _i32p, _i32p]),
-    "dh_surface_price": (C.c_int, [_vp, _vp, _dp, C.c_int64, C.c_int, C.c_double, _dp]),
-    "dh_surface_price_cols": (C.c_int, [_vp, _vp, _dp, _dp, C.c_double, C.c_int64, C.c_int,
-                                        C.c_double, _dp]),
-    "dh_host_register": (C.c_int, [_vp, C.c_size_t]),
-    "dh_host_unregister": (C.c_int, [_vp]),
+    "dh_ctx_set_exact": (_int, [_vp, _int]),
+    "dh_ctx_set_tail_cut": (_int, [_vp, _int]),
+    "dh_ctx_set_path": (_int, [_vp, _int]),
+    "dh_ctx_last_path": (_int, [_vp]),
+    "dh_ctx_debug_stamps": (_int, [_vp, _int]),
+    "dh_ctx_read_stamps": (_int, [_vp, C.POINTER(C.c_ulonglong), _i64, _i64p]),
+    # ---- option surfaces
+    "dh_surface_create": (_int, [_vp, _dp, _dp, _i8p, _dp, _int, _int, C.POINTER(_vp)]),
+    "dh_surface_destroy": (_int, [_vp]),
+    "dh_surface_size": (_int, [_vp, _i32p, _i32p]),
+    "dh_surface_price": (_int, [_vp, _vp, _dp, _i64, _int, _dbl, _dp]),
+    "dh_surface_price_cols": (_int, [_vp, _vp, _dp, _dp, _dbl, _i64, _int, _dbl, _dp]),
+    "dh_host_register": (_int, [_vp, C.c_size_t]),
+    "dh_host_unregister": (_int, [_vp]),
     # the per-iteration calibration call takes raw addresses (ndarray.ctypes.data): half the
     # marshalling cost of data_as() pointers
-    "dh_surface_loss": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp]),
-    "dh_surface_price_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_double, _vp, _vp]),
-    "dh_surface_loss_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp,
-                                      _vp]),
-    "dh_calibrate_lbfgs": (C.c_int, [_vp, _vp, _dp, C.c_int, C.c_double, C.c_double, C.c_int,
-                                     C.c_double, C.POINTER(LbOptions), C.POINTER(LbResult),
-                                     _i32p]),
-    "dh_ctx_set_lb_trace": (C.c_int, [_vp, C.c_int64]),
-    "dh_ctx_read_lb_trace": (C.c_int, [_vp, _dp, C.c_int64, C.POINTER(C.c_int64)]),
-    "dh_gen_draw": (C.c_int, [C.POINTER(C.c_uint32), _i32p, _i32p, _dp, C.c_int64, _dp, _dp,
-                              C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
-                              _dp, _dp, _dp]),
-    "dh_gen_draw_progress": (C.c_int, [C.POINTER(C.c_uint32), _i32p, _i32p, _dp, C.c_int64, _dp,
-                                       _dp, C.c_int, C.c_double, C.c_double, C.c_double,
-                                       C.c_double, C.c_double, _dp, _dp, _dp,
-                                       C.POINTER(C.c_int64)]),
-    "dh_gen_locate": (C.c_int, [C.POINTER(C.c_uint32), _i32p, _i32p, _dp, C.c_int64, C.c_int,
-                                _vp, C.c_int64, _dp]),
-    "dh_gen_draw_located": (C.c_int, [_dp, _vp, C.c_int64, C.c_int64, _dp, _dp, C.c_int,
-                                      C.c_double, C.c_double, C.c_double, _dp, _dp, _dp]),
-    "dh_gen_sweep": (C.c_int, [_dp, _dp, C.c_int64, C.c_int64, C.c_double, C.c_double, _dp]),
-    "dh_gen_drawn_samples": (C.c_int, [C.POINTER(C.c_int64)]),
-    "dh_gen_assemble": (C.c_int, [_dp, _dp, _dp, _dp, C.c_int64, C.c_int, _dp, _dp, _dp]),
-    "dh_gen_dates": (C.c_int, [C.c_int64, C.c_int64, _vp]),
-    "dh_gen_device": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32), _i32p, _i32p, _dp, C.c_int64,
-                                _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_double,
-                                C.c_double, C.c_double, C.c_int, C.c_double, _dp, C.c_int64,
-                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp]),
-    "dh_gen_log": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
-    "dh_math_probe": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, _vp, _vp]),
-    "dh_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_vp)]),
-    "dh_host_free": (C.c_int, [_vp]),
-    "dh_host_cache_trim": (C.c_int, []),
-    "dh_price_batch": (C.c_int, [_vp, _dp, C.c_int64, _dp, _dp, _i8p, C.c_int, C.c_int,
-                                 C.c_double, _dp]),
-    "dh_loss_batch": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _i8p, _dp, C.c_int, C.c_double,
-                                C.c_double, C.c_int, C.c_double, _dp, _i32p]),
-    "dh_surface_fg": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int,
-                                C.c_double, _vp, _vp, _vp]),
-    "dh_surface_fg_begin": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double,
-                                      C.c_int, C.c_double, C.c_int]),
-    "dh_surface_fg_end": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
-    "dh_surface_fg_cancel": (C.c_int, [_vp, C.c_int]),
-    "dh_price_pairs": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_double, _vp]),
-    "dh_implied_vol": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
-    "dh_implied_vol_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
-    "dh_surface_implied_vol": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_double, _vp,
-                                         _vp]),
-    "dh_surface_set_iv_market": (C.c_int, [_vp, _vp, _vp]),
-    "dh_surface_iv_sse_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
-    "dh_surface_loss_iv_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp,
-                                         _vp, _vp, _vp]),
-    "dh_surface_loss_iv": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp,
-                                     _vp]),
-    "dh_surface_loss_rows_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
-    "dh_surface_loss_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
-                                       C.c_double, _vp, _vp, _vp]),
-    "dh_calibrate_lbfgs_batch": (C.c_int, [_vp, _vp, _dp, _dp, _dp, C.c_int, _dp, _i32p, C.c_int,
-                                           C.c_int, C.c_double, C.POINTER(LbOptions),
-                                           C.POINTER(LbResult), _i32p]),
-    "dh_surface_iv_sse_rows_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp,
-                                             _vp, _vp]),
-    "dh_surface_loss_iv_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
-                                          C.c_double, _vp, _vp, _vp, _vp]),
-    "dh_calibrate_lbfgs_batch_iv": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, C.c_int, _dp, _i32p,
-                                              C.c_int, C.c_int, C.c_double, C.POINTER(LbOptions),
-                                              C.POINTER(LbResult), _i32p]),
-    "dh_cf":(C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, _dp, _dp]),
-    "dh_cf_complex": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp]),
-    "dh_trunc_range": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int64, C.c_double, _dp, _dp]),
-    "dh_cos_coeffs": (C.c_int, [_vp, _i32p, C.c_int, C.c_double, C.c_double, C.c_double,
-                                C.c_double, _dp, _dp]),
-    "dh_comm_id": (C.c_int, [_vp]),
-    "dh_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
-    "dh_comm_destroy": (C.c_int, [_vp]),
-    "dh_comm_broadcast": (C.c_int, [_vp, _vp, C.c_int64, C.c_int]),
-    "dh_allgather_best": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i32p]),
-    "dh_comm_allgather": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
-    "dh_best_start": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, C.c_int, _i32p]),
+    "dh_surface_loss": (_int, [_vp, _vp, _vp, _int, _int, _dbl, _vp, _vp, _vp]),
+    "dh_surface_price_dev": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp, _vp]),
+    "dh_surface_loss_dev": (_int, [_vp, _vp, _vp, _int, _int, _dbl, _vp, _vp, _vp, _vp]),
+    "dh_surface_fg": (_int, [_vp, _vp, _vp, _vp, _int, _dbl, _dbl, _int, _dbl, _vp, _vp, _vp]),
+    "dh_surface_fg_begin": (_int, [_vp, _vp, _vp, _vp, _int, _dbl, _dbl, _int, _dbl, _int]),
+    "dh_surface_fg_end": (_int, [_vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "dh_surface_fg_cancel": (_int, [_vp, _int]),
+    # ---- device-resident multi-start L-BFGS-B
+    "dh_calibrate_lbfgs": (_int, [_vp, _vp, _dp, _int, _dbl, _dbl, _int, _dbl, _lbo, _lbr,
+                                  _i32p]),
+    "dh_ctx_set_lb_trace": (_int, [_vp, _i64]),
+    "dh_ctx_read_lb_trace": (_int, [_vp, _dp, _i64, _i64p]),
+    # ---- one-shot forms
+    "dh_price_batch": (_int, [_vp, _dp, _i64, _dp, _dp, _i8p, _int, _int, _dbl, _dp]),
+    "dh_loss_batch": (_int, [_vp, _dp, _int, _dp, _dp, _i8p, _dp, _int, _dbl, _dbl, _int, _dbl,
+                             _dp, _i32p]),
+    # ---- generator batch path: host RNG
+    "dh_gen_draw": (_int, [_u32p, _i32p, _i32p, _dp, _i64, _dp, _dp, _int, _dbl, _dbl, _dbl,
+                           _dbl, _dbl, _dp, _dp, _dp]),
+    "dh_gen_draw_progress": (_int, [_u32p, _i32p, _i32p, _dp, _i64, _dp, _dp, _int, _dbl, _dbl,
+                                    _dbl, _dbl, _dbl, _dp, _dp, _dp, _i64p]),
+    # ---- sharded draw
+    "dh_gen_locate": (_int, [_u32p, _i32p, _i32p, _dp, _i64, _int, _vp, _i64, _dp]),
+    "dh_gen_draw_located": (_int, [_dp, _vp, _i64, _i64, _dp, _dp, _int, _dbl, _dbl, _dbl, _dp,
+                                   _dp, _dp]),
+    "dh_gen_sweep": (_int, [_dp, _dp, _i64, _i64, _dbl, _dbl, _dp]),
+    "dh_gen_drawn_samples": (_int, [_i64p]),
+    "dh_gen_dates": (_int, [_i64, _i64, _vp]),
+    "dh_gen_assemble": (_int, [_dp, _dp, _dp, _dp, _i64, _int, _dp, _dp, _dp]),
+    "dh_gen_device": (_int, [_vp, _vp, _u32p, _i32p, _i32p, _dp, _i64, _dp, _dp, _dbl, _dbl,
+                             _dbl, _dbl, _dbl, _dbl, _int, _dbl, _dp, _i64, _vp, _vp, _vp, _vp,
+                             _vp, _vp, _vp, _dp]),
+    "dh_gen_log": (_int, [_vp, _vp, _i64, _vp]),
+    "dh_math_probe": (_int, [_vp, _int, _vp, _vp, _i64, _vp, _vp]),
+    "dh_host_alloc": (_int, [C.c_size_t, C.POINTER(_vp)]),
+    "dh_host_free": (_int, [_vp]),
+    "dh_host_cache_trim": (_int, []),
+    # ---- paired pricing
+    "dh_price_pairs": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _dbl, _vp]),
+    # ---- Black-Scholes implied volatility
+    "dh_implied_vol": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "dh_implied_vol_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "dh_surface_implied_vol": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp, _vp]),
+    # ---- calibration objective in implied-vol space
+    "dh_surface_set_iv_market": (_int, [_vp, _vp, _vp]),
+    "dh_surface_iv_sse_dev": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
+    "dh_surface_loss_iv_dev": (_int, [_vp, _vp, _vp, _int, _int, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "dh_surface_loss_iv": (_int, [_vp, _vp, _vp, _int, _int, _dbl, _vp, _vp, _vp, _vp]),
+    # ---- many markets on one option grid
+    "dh_surface_loss_rows_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "dh_surface_loss_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _int, _dbl, _vp, _vp,
+                                    _vp]),
+    "dh_calibrate_lbfgs_batch": (_int, [_vp, _vp, _dp, _dp, _dp, _int, _dp, _i32p, _int, _int,
+                                        _dbl, _lbo, _lbr, _i32p]),
+    # ---- many markets on one grid, in implied-vol space
+    "dh_surface_iv_sse_rows_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp,
+                                          _vp]),
+    "dh_surface_loss_iv_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _dbl, _vp,
+                                       _vp, _vp, _vp]),
+    "dh_calibrate_lbfgs_batch_iv": (_int, [_vp, _vp, _dp, _dp, _dp, _dp, _int, _dp, _i32p, _int,
+                                           _int, _dbl, _lbo, _lbr, _i32p]),
+    # ---- building blocks
+    "dh_cf": (_int, [_vp, _dp, _dp, _int, _dbl, _dp, _dp]),
+    "dh_cf_complex": (_int, [_vp, _dp, _dp, _dp, _int, _dbl, _dp, _dp]),
+    "dh_trunc_range": (_int, [_vp, _dp, _dp, _dp, _i64, _dbl, _dp, _dp]),
+    "dh_cos_coeffs": (_int, [_vp, _i32p, _int, _dbl, _dbl, _dbl, _dbl, _dp, _dp]),
+    # ---- multi-GPU: RCCL communicator
+    "dh_comm_id": (_int, [_vp]),
+    "dh_comm_create": (_int, [_vp, _vp, _int, _int, C.POINTER(_vp)]),
+    "dh_comm_destroy": (_int, [_vp]),
+    "dh_comm_broadcast": (_int, [_vp, _vp, _i64, _int]),
+    "dh_comm_allgather": (_int, [_vp, _vp, _i64, _vp]),
+    "dh_allgather_best": (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _i32p]),
+    "dh_best_start": (_int, [_vp, _i64, _int, _int, _int, _i32p]),
+    # ---- Monte Carlo path pricer
+    "dh_mc_price": (_int, [_vp, _vp, _i64, _mco, _int, _i64, _int, C.c_uint64, _vp, _vp]),
+    "dh_mc_price_dev": (_int, [_vp, _vp, _i64, _mco, _int, _i64, _int, C.c_uint64, _vp, _vp,
+                               _vp]),
+    "dh_mc_paths": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _i64, _int, C.c_uint64, _vp]),
 }
 
 
@@ -223,6 +225,9 @@ def device_count() -> int:
     return n.value if rc == 0 else 0
 
 
+# ---- marshalling steps shared by the wrappers below: a _vp argument of SIGNATURES takes a raw
+# address (ndarray.ctypes.data, a device address, _addr() where it may be NULL), a typed pointer
+# argument takes _ptr()
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
@@ -231,7 +236,113 @@ def _ptr(a, ty=_dp):
     return a.ctypes.data_as(ty)
 
 
-class Context:
+def _records(a):
+    """Param records as a contiguous float64 [P, PARAM_STRIDE]."""
+    return _f64(a).reshape(-1, PARAM_STRIDE)
+
+
+def _flags(is_call, n):
+    """Option flags (call = non-zero) as a contiguous int8 [n]."""
+    return np.ascontiguousarray(is_call, dtype=np.int8).reshape(n)
+
+
+def _addr(a, n=1):
+    """Raw address of ndarray / integer address a, or None (NULL) if a is None or 0, or n is 0."""
+    if a is None or not n:
+        return None
+    return a.ctypes.data if isinstance(a, np.ndarray) else (int(a) or None)
+
+
+def _out_array(a, shape, exc, msg, writeable=True):
+    """a if a C-contiguous (writeable) float64 ndarray of shape, else exc(msg); None: a new one."""
+    if a is None:
+        return np.empty(shape)
+    if (not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.shape != shape
+            or not a.flags.c_contiguous or (writeable and not a.flags.writeable)):
+        raise exc(msg)
+    return a
+
+
+def _fd_model(model, S):
+    """An FD request's ``model`` (None, or [2, S, 13]) as a contiguous float64 array."""
+    if model is not None:
+        model = _f64(model)
+        if model.shape != (2, S, 13):
+            raise ValueError(f"model must be [2, {S}, 13], got {model.shape}")
+    return model
+
+
+def _stream_handle(who, stream):
+    """stream (a torch stream, a raw hipStream_t, None) as a raw handle: None -> 0, null refused."""
+    st = 0 if stream is None else int(getattr(stream, "cuda_stream", stream))
+    if stream is not None and st == 0:
+        raise ValueError(f"{who}: the default (null) stream cannot be named; pass a "
+                         "non-default stream, or None for the context's stream")
+    return st
+
+
+def _loss_outputs(S, M, want_prices, want_iv=None):
+    """-> sse [S], n_bad [S], prices, iv [S, M] (None unless wanted) and the wrapper's return tuple:
+    (sse, n_bad, prices or None) in price space (want_iv None), only what is wanted in vol space."""
+    outs = (np.empty(S), np.empty(S, dtype=np.int32),
+            np.empty((S, M)) if want_prices else None, np.empty((S, M)) if want_iv else None)
+    return (*outs, outs[:3] if want_iv is None else tuple(o for o in outs if o is not None))
+
+
+def _lbfgs(name, ctx, surf, S, args, maxiter, maxfun, maxls, chunk, ftol, gtol):
+    """Run a dh_calibrate_lbfgs* export; args: those between surface and options -> (results, n)."""
+    opt = LbOptions(int(maxiter), int(maxfun), int(maxls), int(chunk), float(ftol), float(gtol))
+    res = (LbResult * max(S, 1))()
+    nl = C.c_int32(0)
+    with ctx._lock:
+        _check(getattr(load(), name)(ctx.handle, surf.handle, *args, C.byref(opt), res,
+                                     C.byref(nl)))
+    return list(res)[:S], nl.value
+
+
+class _RngState:
+    """NumPy's legacy RandomState state (np.random's, or a ``get_state()``-style tuple) as the
+    cells the dh_gen_* exports advance in place: key [624] uint32, pos, has_gauss, cached."""
+
+    def __init__(self, state=None):
+        name, key, pos, has_gauss, cached = np.random.get_state() if state is None else state
+        if name != "MT19937":
+            raise NativeError(f"unsupported bit generator {name}")
+        self.key = np.ascontiguousarray(key, dtype=np.uint32).copy()
+        self.pos, self.has_gauss = C.c_int32(int(pos)), C.c_int32(int(has_gauss))
+        self.cached = C.c_double(float(cached))
+
+    def args(self):
+        """The four state arguments of a dh_gen_* export."""
+        return (_ptr(self.key, _u32p), C.byref(self.pos), C.byref(self.has_gauss),
+                C.byref(self.cached))
+
+    def values(self):
+        """-> (key, pos, has_gauss, cached) as advanced."""
+        return self.key, self.pos.value, self.has_gauss.value, self.cached.value
+
+    def restore(self):
+        """Make the advanced state np.random's."""
+        np.random.set_state(("MT19937",) + self.values())
+
+
+class _Handle:
+    """Owner of one library object, its handle in ``_h`` (None once closed): the ``handle``
+    property, and the subclass's ``close()`` when the owner is collected."""
+    _h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Context(_Handle):
     """A device context: one HIP stream + grow-only device scratch (dh_ctx)."""
 
     def __init__(self, device: int = 0):
@@ -245,10 +356,6 @@ class Context:
         # count of the request in flight in each (None = idle), which sizes fg_end's outputs
         self._fg_s = [None] * FG_SLOTS
         self._settings = {}            # set_exact / set_tail_cut / set_path, for slot contexts
-
-    @property
-    def handle(self):
-        return self._h
 
     @property
     def stream(self) -> int:
@@ -285,7 +392,7 @@ class Context:
         _check(load().dh_ctx_read_stamps(self._h, None, 0, C.byref(n)))
         out = np.zeros(n.value, dtype=np.uint64)
         if n.value:
-            _check(load().dh_ctx_read_stamps(self._h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+            _check(load().dh_ctx_read_stamps(self._h, _ptr(out, C.POINTER(C.c_ulonglong)),
                                              n.value, C.byref(n)))
         return out.reshape(-1, STAMPS_PER_BLOCK)
 
@@ -335,22 +442,16 @@ class Context:
             surf.close()
         for c in self.__dict__.pop("_slot_ctxs", {}).values():
             c.close()
-        if getattr(self, "_h", None):
+        if self._h:
             load().dh_ctx_destroy(self._h)
             self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # ---- pricing primitives -------------------------------------------------------------
     def price_pairs(self, params, K, T, is_call, N=128, L=10.0):
-        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        params = _records(params)
         P = params.shape[0]
         K, T = _f64(K).reshape(P), _f64(T).reshape(P)
-        ic = np.ascontiguousarray(is_call, dtype=np.int8).reshape(P)
+        ic = _flags(is_call, P)
         out = np.empty(P)
         with self._lock:
             _check(load().dh_price_pairs(self._h, params.ctypes.data, K.ctypes.data, T.ctypes.data,
@@ -359,11 +460,11 @@ class Context:
 
     def price_batch(self, params, K, T, is_call, N=128, L=10.0):
         """dh_price_batch: out [P, M] for every (param set, option); a surface per call."""
-        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        params = _records(params)
         P = params.shape[0]
         K, T = _f64(K).reshape(-1), _f64(T).reshape(-1)
         M = K.size
-        ic = np.ascontiguousarray(is_call, dtype=np.int8).reshape(M)
+        ic = _flags(is_call, M)
         out = np.empty((P, M))
         with self._lock:
             _check(load().dh_price_batch(self._h, _ptr(params), P, _ptr(K), _ptr(T),
@@ -377,7 +478,7 @@ class Context:
         S = X.shape[0]
         K, T, mkt = _f64(K).reshape(-1), _f64(T).reshape(-1), _f64(mkt).reshape(-1)
         M = K.size
-        ic = np.ascontiguousarray(is_call, dtype=np.int8).reshape(M)
+        ic = _flags(is_call, M)
         loss, bad = np.empty(S), np.empty(S, dtype=np.int32)
         with self._lock:
             _check(load().dh_loss_batch(self._h, _ptr(X), S, _ptr(K), _ptr(T), _ptr(ic, _i8p),
@@ -403,20 +504,19 @@ class Context:
         (float64; is_call int8 / bool) -> sigma [n] (NaN where no vol exists, include/dhcos.h)."""
         cols = [_f64(a).reshape(-1) for a in (price, S0, K, T, r, q)]
         n = cols[0].size
-        ic = np.ascontiguousarray(is_call, dtype=np.int8).reshape(-1)
+        ic = _flags(is_call, -1)
         if any(c.size != n for c in cols) or ic.size != n:
             raise ValueError("implied_vol: every argument must have the same length")
         out = np.empty(n)
         with self._lock:
-            _check(load().dh_implied_vol(self._h, *(c.ctypes.data if n else None for c in cols),
-                                         ic.ctypes.data if n else None, n,
-                                         out.ctypes.data if n else None))
+            _check(load().dh_implied_vol(self._h, *(_addr(c, n) for c in cols), _addr(ic, n), n,
+                                         _addr(out, n)))
         return out
 
     def mc_price(self, records, options, n_paths, steps_per_year, seed):
         """dh_mc_price: records [P, 16], options an array of McOption -> (price, stderr), each
         [P, n_options]."""
-        rec = _f64(records).reshape(-1, PARAM_STRIDE)
+        rec = _records(records)
         P, n_opt = rec.shape[0], len(options)
         price, err = np.empty((P, n_opt)), np.empty((P, n_opt))
         with self._lock:
@@ -438,21 +538,17 @@ class Context:
                              f"cuda:{self.device}")
         P, n_opt = records.shape[0], len(options)
         out = torch.empty((2, P, n_opt), dtype=torch.float64, device=records.device)
-        st = 0 if stream is None else int(getattr(stream, "cuda_stream", stream))
-        if stream is not None and st == 0:
-            raise ValueError("mc_price_dev: the default (null) stream cannot be named; pass a "
-                             "non-default stream, or None for the context's stream")
+        st = _stream_handle("mc_price_dev", stream)
         with self._lock:
-            _check(load().dh_mc_price_dev(self._h, _vp(records.data_ptr()), P, options, n_opt,
+            _check(load().dh_mc_price_dev(self._h, records.data_ptr(), P, options, n_opt,
                                           int(n_paths), int(steps_per_year), int(seed),
-                                          _vp(out[0].data_ptr()), _vp(out[1].data_ptr()),
-                                          _vp(st)))
+                                          out[0].data_ptr(), out[1].data_ptr(), _addr(st)))
         return out[0], out[1]
 
     def mc_paths(self, records, obs_steps, path0, n_paths, steps_per_year, seed):
         """dh_mc_paths: records [P, 16], obs_steps int32 [n_obs] -> [P, n_paths, n_obs, 6]
         (S, v1, v2, running max, min, sum)."""
-        rec = _f64(records).reshape(-1, PARAM_STRIDE)
+        rec = _records(records)
         obs = np.ascontiguousarray(obs_steps, dtype=np.int32).reshape(-1)
         out = np.empty((rec.shape[0], int(n_paths), obs.size, 6))
         with self._lock:
@@ -478,13 +574,9 @@ class Context:
                     or t.device.index != self.device):
                 raise ValueError(f"implied_vol_dev: contiguous {dt} tensors of {n} elements on "
                                  f"cuda:{self.device}")
-        st = 0 if stream is None else int(getattr(stream, "cuda_stream", stream))
-        if stream is not None and st == 0:
-            raise ValueError("implied_vol_dev: the default (null) stream cannot be named; pass a "
-                             "non-default stream, or None for the context's stream")
-        _check(load().dh_implied_vol_dev(self._h, *(_vp(c.data_ptr()) for c in cols),
-                                         _vp(is_call.data_ptr()), n, _vp(out.data_ptr()),
-                                         _vp(st) if st else None))
+        st = _stream_handle("implied_vol_dev", stream)
+        _check(load().dh_implied_vol_dev(self._h, *(c.data_ptr() for c in cols),
+                                         is_call.data_ptr(), n, out.data_ptr(), _addr(st)))
         return out
 
     def cf(self, params16, u, tau):
@@ -507,7 +599,7 @@ class Context:
         return re + 1j * im
 
     def trunc_range(self, params, K, T, L=10.0):
-        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        params = _records(params)
         P = params.shape[0]
         K, T = _f64(K).reshape(P), _f64(T).reshape(P)
         a, b = np.empty(P), np.empty(P)
@@ -586,7 +678,7 @@ def iv_rows(M, mkt_iv, weights):
     return iv, w
 
 
-class Surface:
+class Surface(_Handle):
     """An option set resident in HBM, grouped by maturity into <=256-option tiles (dh_surface)."""
 
     def __init__(self, ctx: Context, K, T, is_call, mkt=None, strike_mode=STRIKE_ABSOLUTE):
@@ -595,7 +687,7 @@ class Surface:
         M = K.size
         if T.size != M:
             raise ValueError("K and T differ in length")
-        ic = np.ascontiguousarray(is_call, dtype=np.int8).reshape(M)
+        ic = _flags(is_call, M)
         mk = None if mkt is None else _f64(mkt).reshape(M)
         h = _vp()
         _check(load().dh_surface_create(ctx.handle, _ptr(K), _ptr(T), _ptr(ic, _i8p),
@@ -607,30 +699,21 @@ class Surface:
         _check(load().dh_surface_size(h, C.byref(m), C.byref(nt)))
         self.n_tiles = nt.value
 
-    @property
-    def handle(self):
-        return self._h
-
     def close(self):
-        if getattr(self, "_h", None):
+        if self._h:
             load().dh_surface_destroy(self._h)
             self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _market_rows(self, mkt):
+        """Market rows (prices or vols) as a contiguous float64 [B, M]."""
+        return _f64(mkt).reshape(-1, self.M) if self.M else _f64(mkt).reshape(len(mkt), 0)
 
     def price(self, params, N=128, L=10.0, out=None):
         """Prices [P, M] of every param row (out: a C-contiguous float64 [P, M] to write into)."""
-        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        params = _records(params)
         P = params.shape[0]
-        if out is None:
-            out = np.empty((P, self.M))
-        elif (out.dtype != np.float64 or out.shape != (P, self.M)
-              or not out.flags.c_contiguous or not out.flags.writeable):
-            raise ValueError(f"out must be a writeable C-contiguous float64 [{P}, {self.M}]")
+        out = _out_array(out, (P, self.M), ValueError,
+                         f"out must be a writeable C-contiguous float64 [{P}, {self.M}]")
         with self.ctx._lock:
             _check(load().dh_surface_price(self.ctx.handle, self._h, _ptr(params), P, int(N),
                                            float(L), _ptr(out)))
@@ -644,11 +727,8 @@ class Surface:
         P = params.shape[0]
         if spots.size != P:
             raise ValueError("params and spots differ in length")
-        if out is None:
-            out = np.empty((P, self.M))
-        elif (out.dtype != np.float64 or out.shape != (P, self.M)
-              or not out.flags.c_contiguous or not out.flags.writeable):
-            raise ValueError(f"out must be a writeable C-contiguous float64 [{P}, {self.M}]")
+        out = _out_array(out, (P, self.M), ValueError,
+                         f"out must be a writeable C-contiguous float64 [{P}, {self.M}]")
         with self.ctx._lock:
             _check(load().dh_surface_price_cols(self.ctx.handle, self._h, _ptr(params),
                                                 _ptr(spots), float(r), P, int(N), float(L),
@@ -657,16 +737,14 @@ class Surface:
 
     def loss_terms(self, params, N=128, L=10.0, want_prices=False):
         """-> (sse[S], n_bad[S], prices[S,M] or None)."""
-        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        params = _records(params)
         S = params.shape[0]
-        sse = np.empty(S)
-        bad = np.empty(S, dtype=np.int32)
-        prices = np.empty((S, self.M)) if want_prices else None
+        sse, bad, prices, _, ret = _loss_outputs(S, self.M, want_prices)
         with self.ctx._lock:
             _check(load().dh_surface_loss(self.ctx.handle, self._h, params.ctypes.data, S, int(N),
                                           float(L), sse.ctypes.data, bad.ctypes.data,
                                           None if prices is None else prices.ctypes.data))
-        return sse, bad, prices
+        return ret
 
     def calibrate_lbfgs(self, x0s, S0, r, N=128, L=10.0, *, maxiter=300, maxfun=15000, maxls=20,
                         ftol=1e-9, gtol=1e-6, chunk=8, ctx=None):
@@ -674,46 +752,36 @@ class Surface:
         ctx: the context (stream and scratch) to run on, default the surface's; a surface may be
         used by several contexts of its device at once.
         -> (list of LbResult, number of loss launches)."""
-        ctx = ctx or self.ctx
         x0s = _f64(x0s).reshape(-1, 13)
         S = x0s.shape[0]
-        opt = LbOptions(int(maxiter), int(maxfun), int(maxls), int(chunk), float(ftol),
-                        float(gtol))
-        res = (LbResult * max(S, 1))()
-        nl = C.c_int32(0)
-        with ctx._lock:
-            _check(load().dh_calibrate_lbfgs(ctx.handle, self._h, _ptr(x0s), S, float(S0),
-                                             float(r), int(N), float(L), C.byref(opt), res,
-                                             C.byref(nl)))
-        return list(res)[:S], nl.value
+        return _lbfgs("dh_calibrate_lbfgs", ctx or self.ctx, self, S,
+                      (_ptr(x0s), S, float(S0), float(r), int(N), float(L)),
+                      maxiter, maxfun, maxls, chunk, ftol, gtol)
 
     def loss_terms_rows(self, params, mkt, row, N=128, L=10.0, want_prices=False):
         """dh_surface_loss_rows -> (sse[S], n_bad[S], prices[S,M] or None): the squared relative
         price errors of every param row against row mkt[row[s]] of the market prices mkt [B, M]
         (the surface's option order), and the count of invalid prices."""
-        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        params = _records(params)
         S = params.shape[0]
-        mkt = _f64(mkt).reshape(-1, self.M) if self.M else _f64(mkt).reshape(len(mkt), 0)
+        mkt = self._market_rows(mkt)
         B = mkt.shape[0]
         row = np.ascontiguousarray(row, dtype=np.int32).reshape(-1)
         if row.size != S:
             raise ValueError("params and row differ in length")
-        sse = np.empty(S)
-        bad = np.empty(S, dtype=np.int32)
-        prices = np.empty((S, self.M)) if want_prices else None
+        sse, bad, prices, _, ret = _loss_outputs(S, self.M, want_prices)
         with self.ctx._lock:
             _check(load().dh_surface_loss_rows(self.ctx.handle, self._h, params.ctypes.data,
                                                mkt.ctypes.data, row.ctypes.data, S, B, int(N),
                                                float(L), sse.ctypes.data, bad.ctypes.data,
-                                               None if prices is None else prices.ctypes.data))
-        return sse, bad, prices
+                                               _addr(prices)))
+        return ret
 
     def loss_rows_dev(self, d_prices: int, d_mkt: int, d_row: int, S: int, d_sse: int, d_bad: int,
                       stream: int = 0):
         """dh_surface_loss_rows_dev: the per-row reduction over [S, M] prices on the device."""
-        _check(load().dh_surface_loss_rows_dev(self.ctx.handle, self._h, _vp(d_prices),
-                                               _vp(d_mkt), _vp(d_row), int(S), _vp(d_sse),
-                                               _vp(d_bad), _vp(stream) if stream else None))
+        _check(load().dh_surface_loss_rows_dev(self.ctx.handle, self._h, d_prices, d_mkt, d_row,
+                                               int(S), d_sse, d_bad, _addr(stream)))
 
     def calibrate_lbfgs_batch(self, mkt, spots, rates, x0s, market_of, N=128, L=10.0, *,
                               maxiter=300, maxfun=15000, maxls=20, ftol=1e-9, gtol=1e-6, chunk=8,
@@ -722,19 +790,11 @@ class Surface:
         (dh_calibrate_lbfgs_batch): row i of x0s [S, 13] fits market market_of[i] -- market
         prices mkt[b] of mkt [B, M], spot spots[b], rate rates[b].
         -> (list of LbResult, number of iterations enqueued)."""
-        ctx = ctx or self.ctx
         mkt, spots, rates, x0s, mof = lb_batch_args(self.M, mkt, spots, rates, x0s, market_of)
         B, S = mkt.shape[0], x0s.shape[0]
-        opt =LbOptions(int(maxiter), int(maxfun), int(maxls), int(chunk), float(ftol),
-                        float(gtol))
-        res = (LbResult * max(S, 1))()
-        nl = C.c_int32(0)
-        with ctx._lock:
-            _check(load().dh_calibrate_lbfgs_batch(ctx.handle, self._h, _ptr(mkt), _ptr(spots),
-                                                   _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p),
-                                                   S, int(N), float(L), C.byref(opt), res,
-                                                   C.byref(nl)))
-        return list(res)[:S], nl.value
+        return _lbfgs("dh_calibrate_lbfgs_batch", ctx or self.ctx, self, S,
+                      (_ptr(mkt), _ptr(spots), _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p), S,
+                       int(N), float(L)), maxiter, maxfun, maxls, chunk, ftol, gtol)
 
     def loss_terms_iv_rows(self, params, mkt_iv, row, N=128, L=10.0, weights=None,
                            want_prices=False, want_iv=False):
@@ -742,10 +802,9 @@ class Surface:
         squared vol errors of every param row (inverted under its own spot, rate and q) against
         row mkt_iv[row[s]] of the market vols mkt_iv [B, M] under weights [B, M] (None: all 1),
         and the count of weighted options without a vol; iv holds the vols as used."""
-        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        params = _records(params)
         S = params.shape[0]
-        mkt_iv = (_f64(mkt_iv).reshape(-1, self.M) if self.M
-                  else _f64(mkt_iv).reshape(len(mkt_iv), 0))
+        mkt_iv = self._market_rows(mkt_iv)
         B = mkt_iv.shape[0]
         w = None
         if weights is not None:
@@ -755,28 +814,21 @@ class Surface:
         row = np.ascontiguousarray(row, dtype=np.int32).reshape(-1)
         if row.size != S:
             raise ValueError("params and row differ in length")
-        sse = np.empty(S)
-        bad = np.empty(S, dtype=np.int32)
-        prices = np.empty((S, self.M)) if want_prices else None
-        iv = np.empty((S, self.M)) if want_iv else None
+        sse, bad, prices, iv, ret = _loss_outputs(S, self.M, want_prices, bool(want_iv))
         with self.ctx._lock:
             _check(load().dh_surface_loss_iv_rows(
-                self.ctx.handle, self._h, params.ctypes.data, mkt_iv.ctypes.data,
-                None if w is None else w.ctypes.data, row.ctypes.data, S, B, int(N), float(L),
-                sse.ctypes.data, bad.ctypes.data,
-                None if prices is None else prices.ctypes.data,
-                None if iv is None else iv.ctypes.data))
-        return (sse, bad) + ((prices,) if want_prices else ()) + ((iv,) if want_iv else ())
+                self.ctx.handle, self._h, params.ctypes.data, mkt_iv.ctypes.data, _addr(w),
+                row.ctypes.data, S, B, int(N), float(L), sse.ctypes.data, bad.ctypes.data,
+                _addr(prices), _addr(iv)))
+        return ret
 
     def iv_sse_rows_dev(self, d_params: int, d_prices: int, d_mkt_iv: int, d_wgt: int, d_row: int,
                         S: int, d_sse: int, d_bad: int, d_iv: int = 0, stream: int = 0):
         """dh_surface_iv_sse_rows_dev: the per-row vol-space reduction over [S, M] prices on the
         device."""
-        _check(load().dh_surface_iv_sse_rows_dev(self.ctx.handle, self._h, _vp(d_params),
-                                                 _vp(d_prices), _vp(d_mkt_iv), _vp(d_wgt),
-                                                 _vp(d_row), int(S), _vp(d_sse), _vp(d_bad),
-                                                 _vp(d_iv) if d_iv else None,
-                                                 _vp(stream) if stream else None))
+        _check(load().dh_surface_iv_sse_rows_dev(self.ctx.handle, self._h, d_params, d_prices,
+                                                 d_mkt_iv, d_wgt, d_row, int(S), d_sse, d_bad,
+                                                 _addr(d_iv), _addr(stream)))
 
     def calibrate_lbfgs_batch_iv(self, mkt_iv, weights, spots, rates, x0s, market_of, N=128,
                                  L=10.0, *, maxiter=300, maxfun=15000, maxls=20, ftol=1e-9,
@@ -785,21 +837,14 @@ class Surface:
         [S, 13] fits the vols mkt_iv[b] of market b = market_of[i] under weights[b] (weights
         [B, M], [M] or None for all 1), spot spots[b], rate rates[b].
         -> (list of LbResult, number of iterations enqueued)."""
-        ctx = ctx or self.ctx
         mkt_iv, spots, rates, x0s, mof = lb_batch_args(self.M, mkt_iv, spots, rates, x0s,
                                                        market_of)
         mkt_iv, w = iv_rows(self.M, mkt_iv, weights)
         B, S = mkt_iv.shape[0], x0s.shape[0]
-        opt = LbOptions(int(maxiter), int(maxfun), int(maxls), int(chunk), float(ftol),
-                        float(gtol))
-        res = (LbResult * max(S, 1))()
-        nl = C.c_int32(0)
-        with ctx._lock:
-            _check(load().dh_calibrate_lbfgs_batch_iv(ctx.handle, self._h, _ptr(mkt_iv), _ptr(w),
-                                                      _ptr(spots), _ptr(rates), B, _ptr(x0s),
-                                                      _ptr(mof, _i32p), S, int(N), float(L),
-                                                      C.byref(opt), res, C.byref(nl)))
-        return list(res)[:S], nl.value
+        return _lbfgs("dh_calibrate_lbfgs_batch_iv", ctx or self.ctx, self, S,
+                      (_ptr(mkt_iv), _ptr(w), _ptr(spots), _ptr(rates), B, _ptr(x0s),
+                       _ptr(mof, _i32p), S, int(N), float(L)),
+                      maxiter, maxfun, maxls, chunk, ftol, gtol)
 
     def fg(self, X0, S0, r, N=128, L=10.0, model=None):
         """dh_surface_fg: (f [S], g [S, 13], low [S]) of one FD request per row of X0 [S, 13].
@@ -807,10 +852,7 @@ class Surface:
         for libm's exp / tanh in the library."""
         X0 = _f64(X0).reshape(-1, 13)
         S = X0.shape[0]
-        if model is not None:
-            model = _f64(model)
-            if model.shape != (2, S, 13):
-                raise ValueError(f"model must be [2, {S}, 13], got {model.shape}")
+        model = _fd_model(model, S)
         f, g, low = np.empty(S), np.empty((S, 13)), np.empty(S)
         with self.ctx._lock:
             _check(load().dh_surface_fg(self.ctx.handle, self._h, X0.ctypes.data,
@@ -824,10 +866,7 @@ class Surface:
         once; the slot keeps the request until fg_end(slot)."""
         X0 = _f64(X0).reshape(-1, 13)
         S = X0.shape[0]
-        if model is not None:
-            model = _f64(model)
-            if model.shape != (2, S, 13):
-                raise ValueError(f"model must be [2, {S}, 13], got {model.shape}")
+        model = _fd_model(model, S)
         with self.ctx._lock:
             _check(load().dh_surface_fg_begin(self.ctx.handle, self._h, X0.ctypes.data,
                                               None if model is None else model.ctypes.data, S,
@@ -850,14 +889,14 @@ class Surface:
         """dh_surface_implied_vol: the Black-Scholes vols [P, M] of the model prices of every
         param row (S0, r, q from the row), inverted on the device; with want_prices also the
         prices [P, M] (dh_surface_price's bits) -> iv or (iv, prices)."""
-        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        params = _records(params)
         P = params.shape[0]
         iv = np.empty((P, self.M))
         prices = np.empty((P, self.M)) if want_prices else None
         with self.ctx._lock:
             _check(load().dh_surface_implied_vol(self.ctx.handle, self._h, params.ctypes.data, P,
                                                  int(N), float(L), iv.ctypes.data,
-                                                 None if prices is None else prices.ctypes.data))
+                                                 _addr(prices)))
         return (iv, prices) if want_prices else iv
 
     def set_iv_market(self, mkt_iv, weight=None):
@@ -868,54 +907,44 @@ class Surface:
         if iv.size != self.M or (w is not None and w.size != self.M):
             raise ValueError(f"mkt_iv and weight must hold {self.M} values")
         with self.ctx._lock:
-            _check(load().dh_surface_set_iv_market(self._h, iv.ctypes.data,
-                                                   None if w is None else w.ctypes.data))
+            _check(load().dh_surface_set_iv_market(self._h, iv.ctypes.data, _addr(w)))
 
     def loss_terms_iv(self, params, N=128, L=10.0, want_prices=False, want_iv=False):
         """dh_surface_loss_iv -> (sse[S], n_bad[S][, prices[S,M]][, iv[S,M]]): the weighted
         squared vol errors against set_iv_market's vols and the count of weighted options without
         a vol; iv holds the vols as used (0.0 where clamped at the lower bound, NaN where bad)."""
-        params = _f64(params).reshape(-1, PARAM_STRIDE)
+        params = _records(params)
         S = params.shape[0]
-        sse = np.empty(S)
-        bad = np.empty(S, dtype=np.int32)
-        prices = np.empty((S, self.M)) if want_prices else None
-        iv = np.empty((S, self.M)) if want_iv else None
+        sse, bad, prices, iv, ret = _loss_outputs(S, self.M, want_prices, bool(want_iv))
         with self.ctx._lock:
             _check(load().dh_surface_loss_iv(self.ctx.handle, self._h, params.ctypes.data, S,
                                              int(N), float(L), sse.ctypes.data, bad.ctypes.data,
-                                             None if prices is None else prices.ctypes.data,
-                                             None if iv is None else iv.ctypes.data))
-        return (sse, bad) + ((prices,) if want_prices else ()) + ((iv,) if want_iv else ())
+                                             _addr(prices), _addr(iv)))
+        return ret
 
     # device-pointer variants (torch tensors or raw device addresses)
     def price_dev(self, d_params: int, P: int, d_out: int, N=128, L=10.0, stream: int = 0):
-        _check(load().dh_surface_price_dev(self.ctx.handle, self._h, _vp(d_params), int(P), int(N),
-                                           float(L), _vp(d_out), _vp(stream) if stream else None))
+        _check(load().dh_surface_price_dev(self.ctx.handle, self._h, d_params, int(P), int(N),
+                                           float(L), d_out, _addr(stream)))
 
     def loss_dev(self, d_params: int, S: int, d_sse: int, d_bad: int, d_prices: int = 0, N=128,
                  L=10.0, stream: int = 0):
-        _check(load().dh_surface_loss_dev(self.ctx.handle, self._h, _vp(d_params), int(S), int(N),
-                                          float(L), _vp(d_sse), _vp(d_bad),
-                                          _vp(d_prices) if d_prices else None,
-                                          _vp(stream) if stream else None))
+        _check(load().dh_surface_loss_dev(self.ctx.handle, self._h, d_params, int(S), int(N),
+                                          float(L), d_sse, d_bad, _addr(d_prices),
+                                          _addr(stream)))
 
     def iv_sse_dev(self, d_params: int, d_prices: int, S: int, d_sse: int, d_bad: int,
                    d_iv: int = 0, stream: int = 0):
         """dh_surface_iv_sse_dev: the vol-space reduction over [S, M] prices on the device."""
-        _check(load().dh_surface_iv_sse_dev(self.ctx.handle, self._h, _vp(d_params),
-                                            _vp(d_prices), int(S), _vp(d_sse), _vp(d_bad),
-                                            _vp(d_iv) if d_iv else None,
-                                            _vp(stream) if stream else None))
+        _check(load().dh_surface_iv_sse_dev(self.ctx.handle, self._h, d_params, d_prices, int(S),
+                                            d_sse, d_bad, _addr(d_iv), _addr(stream)))
 
     def loss_iv_dev(self, d_params: int, S: int, d_sse: int, d_bad: int, d_prices: int = 0,
                     d_iv: int = 0, N=128, L=10.0, stream: int = 0):
         """dh_surface_loss_iv_dev: price, then reduce in vol space, on one stream."""
-        _check(load().dh_surface_loss_iv_dev(self.ctx.handle, self._h, _vp(d_params), int(S),
-                                             int(N), float(L), _vp(d_sse), _vp(d_bad),
-                                             _vp(d_prices) if d_prices else None,
-                                             _vp(d_iv) if d_iv else None,
-                                             _vp(stream) if stream else None))
+        _check(load().dh_surface_loss_iv_dev(self.ctx.handle, self._h, d_params, int(S), int(N),
+                                             float(L), d_sse, d_bad, _addr(d_prices),
+                                             _addr(d_iv), _addr(stream)))
 
 
 class FgChannel:
@@ -1005,9 +1034,6 @@ class FgChannel:
         return self._f[:S].copy(), self._g[:S].copy(), self._low[:S].copy()
 
 
-COMM_ID_BYTES = 128
-
-
 def comm_id() -> bytes:
     """dh_comm_id: a fresh RCCL unique id (rank 0), to be shipped to every rank."""
     buf = C.create_string_buffer(COMM_ID_BYTES)
@@ -1018,15 +1044,15 @@ def comm_id() -> bytes:
 def best_start(records, col_start, col_fun) -> int:
     """dh_best_start: the reference's strict-< best start (lbfgs_calibrator.py:271-275) over
     per-start rows (negative start index = padding); -1 if none."""
-    rec = np.ascontiguousarray(records, dtype=np.float64)
+    rec = _f64(records)
     rows, width = (rec.shape[0], rec.shape[1]) if rec.ndim == 2 else (0, 1)
     best = C.c_int32(-2)
-    _check(load().dh_best_start(rec.ctypes.data if rows else None, rows, width, int(col_start),
-                                int(col_fun), C.byref(best)))
+    _check(load().dh_best_start(_addr(rec, rows), rows, width, int(col_start), int(col_fun),
+                                C.byref(best)))
     return best.value
 
 
-class Comm:
+class Comm(_Handle):
     """dh_comm: an RCCL communicator over the ranks' contexts (one per rank, its device and
     stream), for multi-start sharding without torch.distributed.  Collective construction: every
     rank passes rank 0's ``comm_id()`` bytes."""
@@ -1042,41 +1068,34 @@ class Comm:
         self._h = h
 
     def close(self):
-        if getattr(self, "_h", None):
+        if self._h:
             h, self._h = self._h, None
             _check(load().dh_comm_destroy(h))
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def broadcast(self, buf, root: int = 0) -> np.ndarray:
         """root's float64 values on every rank (in place on a contiguous array; returned)."""
-        out = np.ascontiguousarray(buf, dtype=np.float64)
-        _check(load().dh_comm_broadcast(self._h, out.ctypes.data if out.size else None, out.size,
-                                        int(root)))
+        out = _f64(buf)
+        _check(load().dh_comm_broadcast(self._h, _addr(out, out.size), out.size, int(root)))
         return out
 
     def allgather(self, block) -> np.ndarray:
         """block (float64, same size on every rank) -> [world, *block.shape] in rank order."""
-        blk = np.ascontiguousarray(block, dtype=np.float64)
+        blk = _f64(block)
         out = np.empty((self.world,) + blk.shape)
-        _check(load().dh_comm_allgather(self._h, blk.ctypes.data if blk.size else None, blk.size,
-                                        out.ctypes.data if out.size else None))
+        _check(load().dh_comm_allgather(self._h, _addr(blk, blk.size), blk.size,
+                                        _addr(out, out.size)))
         return out
 
     def allgather_best(self, records, col_start: int, col_fun: int):
         """records [rows, width] of this rank (same rows on every rank) -> ([world * rows, width]
         in rank order, the strict-< best start or -1)."""
-        rec = np.ascontiguousarray(records, dtype=np.float64)
+        rec = _f64(records)
         rows, width = rec.shape
         out = np.empty((self.world * rows, width))
         best = C.c_int32(-2)
-        _check(load().dh_allgather_best(self._h, rec.ctypes.data if rec.size else None, rows,
-                                        width, int(col_start), int(col_fun),
-                                        out.ctypes.data, C.byref(best)))
+        _check(load().dh_allgather_best(self._h, _addr(rec, rec.size), rows, width,
+                                        int(col_start), int(col_fun), out.ctypes.data,
+                                        C.byref(best)))
         return out, best.value
 
 
@@ -1084,19 +1103,13 @@ def gen_draw(n_samples, lo, hi, n_opt, alpha, spot0, ret_mu, ret_sigma, noise_si
     """dh_gen_draw on NumPy's global legacy RandomState: draws the generator's samples natively
     and advances np.random's state exactly as the reference's per-sample calls would.
     -> (params [n, 13], spots [n], noise [n, n_opt])."""
-    name, key, pos, has_gauss, cached = np.random.get_state()
-    if name != "MT19937":
-        raise NativeError(f"unsupported bit generator {name}")
-    key = np.ascontiguousarray(key, dtype=np.uint32).copy()
-    c_pos, c_has, c_cached = C.c_int32(int(pos)), C.c_int32(int(has_gauss)), C.c_double(cached)
+    rng = _RngState()
     n = int(n_samples)
     params, spots, noise = np.empty((n, 13)), np.empty(n), np.empty((n, int(n_opt)))
-    _check(load().dh_gen_draw(key.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(c_pos),
-                              C.byref(c_has), C.byref(c_cached), n, _ptr(_f64(lo)), _ptr(_f64(hi)),
-                              int(n_opt), float(alpha), float(spot0), float(ret_mu),
-                              float(ret_sigma), float(noise_sigma), _ptr(params), _ptr(spots),
-                              _ptr(noise)))
-    np.random.set_state((name, key, c_pos.value, c_has.value, c_cached.value))
+    _check(load().dh_gen_draw(*rng.args(), n, _ptr(_f64(lo)), _ptr(_f64(hi)), int(n_opt),
+                              float(alpha), float(spot0), float(ret_mu), float(ret_sigma),
+                              float(noise_sigma), _ptr(params), _ptr(spots), _ptr(noise)))
+    rng.restore()
     return params, spots, noise
 
 
@@ -1108,13 +1121,7 @@ class GenDraw:
     (params, spots, noise).  np.random must not be used between the two."""
 
     def __init__(self, n_samples, lo, hi, n_opt, alpha, spot0, ret_mu, ret_sigma, noise_sigma):
-        st = np.random.get_state()
-        if st[0] != "MT19937":
-            raise NativeError(f"unsupported bit generator {st[0]}")
-        self._name = st[0]
-        self._key = np.ascontiguousarray(st[1], dtype=np.uint32).copy()
-        self._pos, self._has = C.c_int32(int(st[2])), C.c_int32(int(st[3]))
-        self._cached = C.c_double(st[4])
+        self._rng = _RngState()
         n = self.n = int(n_samples)
         self.params, self.spots = np.empty((n, 13)), np.empty(n)
         self.noise = np.empty((n, int(n_opt)))
@@ -1129,12 +1136,9 @@ class GenDraw:
         self._thread.start()
 
     def _run(self, lib):
-        n_opt, alpha, spot0, ret_mu, ret_sigma, noise_sigma = self._args
         self._rc = lib.dh_gen_draw_progress(
-            self._key.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(self._pos),
-            C.byref(self._has), C.byref(self._cached), self.n, _ptr(self._lo), _ptr(self._hi),
-            n_opt, alpha, spot0, ret_mu, ret_sigma, noise_sigma, _ptr(self.params),
-            _ptr(self.spots), _ptr(self.noise), C.byref(self._done))
+            *self._rng.args(), self.n, _ptr(self._lo), _ptr(self._hi), *self._args,
+            _ptr(self.params), _ptr(self.spots), _ptr(self.noise), C.byref(self._done))
 
     def ready(self, e):
         e = min(int(e), self.n)
@@ -1149,12 +1153,8 @@ class GenDraw:
             self._thread.join()
             self._finished = True
             _check(self._rc if self._rc is not None else -1)   # None: the thread raised
-            np.random.set_state((self._name, self._key, self._pos.value, self._has.value,
-                                 self._cached.value))
+            self._rng.restore()
         return self.params, self.spots, self.noise
-
-
-GEN_LOC_WORDS = 627            # DH_GEN_LOC_WORDS: key[624], pos, has_gauss, cached gauss
 
 
 def gen_locate(state, n_samples, n_opt, starts):
@@ -1163,17 +1163,13 @@ def gen_locate(state, n_samples, n_opt, starts):
     ``n_samples``-sample draw, without drawing the samples -> (loc [len(starts), 627], the state
     the whole draw leaves [627])."""
     st = np.asarray(state, dtype=np.float64).reshape(GEN_LOC_WORDS)
-    key = st[:624].astype(np.uint32)
-    c_pos, c_has = C.c_int32(int(st[624])), C.c_int32(int(st[625]))
-    c_cached = C.c_double(float(st[626]))
+    rng = _RngState(("MT19937", st[:624].astype(np.uint32), st[624], st[625], st[626]))
     starts = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
     loc = np.empty((starts.size, GEN_LOC_WORDS))
-    _check(load().dh_gen_locate(key.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(c_pos),
-                                C.byref(c_has), C.byref(c_cached), int(n_samples), int(n_opt),
-                                starts.ctypes.data if starts.size else None, starts.size,
-                                _ptr(loc)))
-    end = np.concatenate([key.astype(np.float64), [c_pos.value, c_has.value, c_cached.value]])
-    return loc, end
+    _check(load().dh_gen_locate(*rng.args(), int(n_samples), int(n_opt),
+                                _addr(starts, starts.size), starts.size, _ptr(loc)))
+    key, *cells = rng.values()
+    return loc, np.concatenate([key.astype(np.float64), cells])
 
 
 def gen_draw_located(loc, starts, i_end, lo, hi, n_opt, ret_mu, ret_sigma, noise_sigma):
@@ -1201,8 +1197,9 @@ def gen_sweep(params, spots, i0, alpha, spot0, carry):
     this block's last row out (returned)."""
     n = params.shape[0]
     for a, shp in ((params, (n, 13)), (spots, (n,))):
-        if a.dtype != np.float64 or a.shape != shp or not a.flags.c_contiguous:
-            raise NativeError("gen_sweep: params [n, 13] and spots [n] must be C-contiguous float64")
+        _out_array(a, shp, NativeError,
+                   "gen_sweep: params [n, 13] and spots [n] must be C-contiguous float64",
+                   writeable=False)
     carry = np.array(carry, dtype=np.float64).reshape(14)
     _check(load().dh_gen_sweep(_ptr(params), _ptr(spots), int(i0), n, float(alpha), float(spot0),
                                _ptr(carry)))
@@ -1225,15 +1222,11 @@ def gen_assemble(model, noise, spots, k_rel, out=None):
     n, m = model.shape
     if noise.shape != (n, m) or spots.shape != (n,) or k_rel.shape != (m,):
         raise NativeError("gen_assemble: shape mismatch")
-    if out is None:
-        market, loss, strikes = np.empty((n, m)), np.empty(n), np.empty((n, m))
-    else:
-        market, loss, strikes = out
-        for a, shp in ((market, (n, m)), (loss, (n,)), (strikes, (n, m))):
-            if (not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.shape != shp
-                    or not a.flags.c_contiguous or not a.flags.writeable):
-                raise NativeError("gen_assemble: out arrays must be writable C-contiguous float64 "
-                                  "of the input shapes")
+    market, loss, strikes = (None, None, None) if out is None else out
+    market, loss, strikes = (
+        _out_array(a, shp, NativeError, "gen_assemble: out arrays must be writable C-contiguous "
+                   "float64 of the input shapes")
+        for a, shp in ((market, (n, m)), (loss, (n,)), (strikes, (n, m))))
     _check(load().dh_gen_assemble(_ptr(model), _ptr(noise), _ptr(spots), _ptr(k_rel), n, m,
                                   _ptr(market), _ptr(loss), _ptr(strikes)))
     return market, loss, strikes
@@ -1243,7 +1236,7 @@ def gen_dates(first_day, n):
     """dh_gen_dates: n weekday dates from day first_day (a Monday; days since 1970-01-01) as a
     '<U10' array of 'YYYY-MM-DD', or None past year 9999 (the caller formats those)."""
     out = np.empty(int(n), dtype="U10")
-    rc = load().dh_gen_dates(int(first_day), int(n), out.ctypes.data if n else None)
+    rc = load().dh_gen_dates(int(first_day), int(n), _addr(out, n))
     if rc != 0:
         return None
     return out
@@ -1368,8 +1361,7 @@ def gen_log(x, ctx=None) -> np.ndarray:
     x = _f64(x).ravel()
     out = np.empty_like(x)
     ctx = ctx or default_context()
-    _check(load().dh_gen_log(ctx.handle, x.ctypes.data if x.size else None, x.size,
-                             out.ctypes.data if x.size else None))
+    _check(load().dh_gen_log(ctx.handle, _addr(x, x.size), x.size, _addr(out, x.size)))
     return out
 
 
@@ -1407,9 +1399,8 @@ def math_probe(fn_name, x, y=None, ctx=None):
         n //= 2
     out0, out1 = np.empty(n), np.empty(n)
     ctx = ctx or default_context()
-    _check(load().dh_math_probe(ctx.handle, fn, x.ctypes.data if n else None,
-                                y.ctypes.data if two and n else None, n,
-                                out0.ctypes.data if n else None, out1.ctypes.data if n else None))
+    _check(load().dh_math_probe(ctx.handle, fn, _addr(x, n), _addr(y, two and n), n,
+                                _addr(out0, n), _addr(out1, n)))
     return (out0, out1) if fn_name in _PROBE_TWO_OUT else out0
 
 
@@ -1420,11 +1411,7 @@ def gen_device(surf, n_samples, lo, hi, alpha, spot0, ret_mu, ret_sigma, noise_s
     device; np.random's state advanced exactly as the reference's per-sample calls would.  The
     outputs are page-locked arrays (pinned_empty).  -> dict(params, spots, market, model, loss,
     strikes, dates ('<U10', or None when first_day is None))."""
-    name, key, pos, has_gauss, cached = np.random.get_state()
-    if name != "MT19937":
-        raise NativeError(f"unsupported bit generator {name}")
-    key = np.ascontiguousarray(key, dtype=np.uint32).copy()
-    c_pos, c_has, c_cached = C.c_int32(int(pos)), C.c_int32(int(has_gauss)), C.c_double(cached)
+    rng = _RngState()
     n, m = int(n_samples), int(surf.M)
     k_rel = _f64(k_rel).reshape(-1)
     if k_rel.size != m:
@@ -1434,14 +1421,13 @@ def gen_device(surf, n_samples, lo, hi, alpha, spot0, ret_mu, ret_sigma, noise_s
            "loss": pinned_empty(n), "strikes": pinned_empty((n, m)),
            "dates": pinned_empty(n, "U10") if first_day is not None else None}
     st = np.zeros(8) if stats is None else stats
-    addr = {k: (v.ctypes.data if v is not None and v.size else None) for k, v in out.items()}
+    addr = {k: _addr(v, v is None or v.size) for k, v in out.items()}
     _check(load().dh_gen_device(
-        surf.ctx.handle, surf.handle, key.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(c_pos),
-        C.byref(c_has), C.byref(c_cached), n, _ptr(_f64(lo)), _ptr(_f64(hi)), float(alpha),
-        float(spot0), float(ret_mu), float(ret_sigma), float(noise_sigma), float(r), int(N),
-        float(L), _ptr(k_rel), int(first_day or 0), addr["params"], addr["spots"],
+        surf.ctx.handle, surf.handle, *rng.args(), n, _ptr(_f64(lo)), _ptr(_f64(hi)),
+        float(alpha), float(spot0), float(ret_mu), float(ret_sigma), float(noise_sigma), float(r),
+        int(N), float(L), _ptr(k_rel), int(first_day or 0), addr["params"], addr["spots"],
         addr["market"], addr["model"], addr["loss"], addr["strikes"], addr["dates"], _ptr(st)))
-    np.random.set_state((name, key, c_pos.value, c_has.value, c_cached.value))
+    rng.restore()
     return out
 
 
@@ -1457,14 +1443,18 @@ def default_context(device: int | None = None) -> Context:
     return ctx
 
 
-__all__ = ["gen_draw", "gen_assemble", "gen_dates", "gen_locate", "gen_draw_located", "gen_sweep",
-           "gen_drawn_samples", "GEN_LOC_WORDS", "LbOptions", "LbResult", "Context", "Surface", "NativeError", "load", "default_context", "device_count",
-           "runtime_shared_with_torch", "resolve_device", "PARAM_STRIDE", "MAX_N", "MAX_N_PER_TERM",
-           "STRIKE_ABSOLUTE",
-           "STRIKE_PCT_SPOT", "PATH_AUTO", "PATH_SPLIT", "PATH_FUSED", "PATH_GEN",
-           "LIB_PATH",
-           "SIGNATURES",
-           "Comm", "comm_id", "best_start", "COMM_ID_BYTES", "FgChannel", "pinned",
-           "pinned_empty", "host_cache_trim", "gen_device", "gen_log",
-           "math_probe", "MATH_PROBE_FNS", "lb_batch_args",
-           "McOption", "MC_KINDS", "MC_MAX_OPTIONS", "MC_POISSON_CAP"]
+# every public top-level name, in SIGNATURES' groups: the library, context and surfaces, L-BFGS-B,
+# generator, communicator, Monte Carlo
+__all__ = [
+    "LIB_PATH", "SIGNATURES", "NativeError", "load", "runtime_shared_with_torch", "device_count",
+    "resolve_device", "default_context", "PARAM_STRIDE", "MAX_N", "MAX_N_PER_TERM",
+    "STRIKE_ABSOLUTE", "STRIKE_PCT_SPOT", "PATH_AUTO", "PATH_SPLIT", "PATH_FUSED", "PATH_GEN",
+    "FG_SLOTS", "STAMPS_PER_BLOCK",
+    "Context", "Surface", "FgChannel", "pinned", "pinned_empty", "host_cache_trim",
+    "LbOptions", "LbResult", "lb_batch_args", "iv_rows",
+    "gen_draw", "GenDraw", "GEN_LOC_WORDS", "gen_locate", "gen_draw_located", "gen_sweep",
+    "gen_drawn_samples", "gen_dates", "gen_assemble", "gen_device", "gen_log",
+    "MATH_PROBE_FNS", "math_probe",
+    "COMM_ID_BYTES", "Comm", "comm_id", "best_start",
+    "McOption", "MC_KINDS", "MC_MAX_OPTIONS", "MC_POISSON_CAP",
+]
