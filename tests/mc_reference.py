@@ -104,6 +104,8 @@ class Factor:
             stats["psi_gap"] = min(stats["psi_gap"], float(np.min(np.abs(psi - PSI_C))))
             if np.any(~quad):
                 stats["u_gap"] = min(stats["u_gap"], float(np.min(np.abs(u_v - p)[~quad])))
+            if "trace" in stats:
+                stats["trace"] += [quad, ~quad & (u_v <= p)]
         i_v = 0.5 * (v + vn) * self.dt
         dx = (-0.5 * i_v + self.rs * (vn - v - self.ktdt + self.kappa * i_v)
               + np.sqrt(self.omr2 * i_v) * z_s)
@@ -164,6 +166,8 @@ def simulate(params, spot, rate, paths, n_steps, steps_per_year, seed, obs_steps
             stats["n1"] += int(np.sum(nj == 1))
             stats["n2"] += int(np.sum(nj >= 2))
             stats["u_gap"] = min(stats["u_gap"], float(np.min(np.abs(u_n[:, None] - cdf[None, :]))))
+            if "trace" in stats:
+                stats["trace"].append(nj)
         x = x + ((drift + nj * mu_j) + (np.sqrt(nj) * sig_j) * z_j)
         s = spot * np.exp(x)
         mx, mn, sm = np.maximum(mx, s), np.minimum(mn, s), sm + s
@@ -212,3 +216,85 @@ def price(params, spot, rate, options, n_paths, steps_per_year, seed, block=1 <<
     pr = np.array([finish(sums[j, 0], sums[j, 1], steps[j]) for j in range(len(options))])
     fw = np.array([finish(fsum[st][0], fsum[st][1], st) for st in steps])
     return pr[:, 0], pr[:, 1], fw[:, 0], fw[:, 1]
+
+
+# ---- the 50-digit truth fixture (tests/golden/make_mc_truth.py writes it) -------------------------
+def _with(base, **kw):
+    names = ["v01", "kappa1", "theta1", "sigma1", "rho1", "v02", "kappa2", "theta2", "sigma2",
+             "rho2", "lambda_j", "mu_j", "sigma_j"]
+    p = np.array(base, dtype=np.float64)
+    for k, v in kw.items():
+        p[names.index(k)] = v
+    return p
+
+
+# legal edges of the validation: both variances start at 0, no jumps, |rho| next to 1
+ZERO_V0_PARAMS = _with(README_PARAMS, v01=0.0, v02=0.0, lambda_j=0.0, rho1=0.999, rho2=-0.999)
+# lambda dt = 1 exactly at 8 steps per year (the Poisson walk's cap), jumps of one fixed size
+CAP_JUMP_PARAMS = _with(README_PARAMS, lambda_j=8.0, mu_j=-0.04, sigma_j=0.0)
+TRUTH_SETS = np.stack([README_PARAMS, STRESSED_PARAMS, ZERO_V0_PARAMS, CAP_JUMP_PARAMS])
+TRUTH_SEED = 0x9E3779B900000005         # the key's high word is live
+TRUTH_PATHS = np.array(list(range(24)) + list(range(1000, 1004))
+                       + [(1 << 32) - 1, 1 << 32, (1 << 32) + 1, 5 * (1 << 32) + 77],
+                       dtype=np.uint64)  # the counter's high word is 0, 1 and 5
+TRUTH_SPY, TRUTH_OBS, TRUTH_SPOT, TRUTH_RATE = 8, (2, 4, 8), 100.0, 0.03
+TRUTH_FILE = "mc_truth.npz"
+
+
+def truth_restatement(stats=None):
+    """This module's walk of the fixture's configuration -> [4, n_paths, 3, 6]."""
+    return np.stack([simulate(p, TRUTH_SPOT, TRUTH_RATE, TRUTH_PATHS, TRUTH_OBS[-1], TRUTH_SPY,
+                              TRUTH_SEED, TRUTH_OBS, stats)[1] for p in TRUTH_SETS])
+
+
+def truth_errors(got, hi, lo):
+    """got [..., 6] against the truth hi + lo (hi the truth rounded to double, lo the rounded
+    remainder) -> (worst relative error per statistic [6], worst absolute error on v1, v2 [2]).
+    got - hi is exact for neighbours, so the figures resolve far below an ulp without mpmath.
+    Where the truth is an exact 0 the error counts as 0 if got is 0 too, as infinite if not."""
+    d = np.abs((got - hi) - lo)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rel = np.where(hi == 0.0, np.where(got == 0.0, 0.0, np.inf), d / np.abs(hi))
+    flat = (-1, 6)
+    return rel.reshape(flat).max(axis=0), d.reshape(flat)[:, 1:3].max(axis=0)
+
+
+# ---- the moments of the variance factors ---------------------------------------------------------
+def cir_moments(v0, kappa, theta, sigma, T):
+    """Mean and variance of a CIR process at T from v0 (see moment_z_scores)."""
+    e = np.exp(-kappa * T)
+    return (theta + (v0 - theta) * e,
+            v0 * sigma * sigma / kappa * (e - e * e)
+            + theta * sigma * sigma / (2.0 * kappa) * (1.0 - e) ** 2)
+
+
+def moment_z_scores(params, state, spot, rate, T):
+    """state [n, 6]: the statistics of n paths at time T -> {name: |sample - exact| / its
+    standard error} for the mean and the variance of v1 and v2 and for the discounted mean of S.
+
+    Why the exact figures are the CIR closed forms although the scheme is discrete: one QE step
+    from v draws v' with E[v' | v] = m = theta + (v - theta) E and Var[v' | v] = s^2 = v K1 + K2
+    in either branch (quadratic: a (1 + b^2) = m and 2 a^2 (1 + 2 b^2) = s^2 by the choice of b^2;
+    exponential: (1 - p) / beta = m and (1 - p^2) / beta^2 = s^2), and those are the exact
+    conditional moments of the CIR process over dt, E = e^{-kappa dt}.  Both are linear in v, so
+    the towers E[v'] = theta + (E[v] - theta) E and Var[v'] = K1 E[v] + K2 + E^2 Var[v] close on
+    the first two moments, the exact process obeys the same recursion, and after n steps both give
+        E = theta + (v0 - theta) e^{-kappa T},
+        Var = v0 sigma^2 / kappa (e^{-kappa T} - e^{-2 kappa T})
+              + theta sigma^2 / (2 kappa) (1 - e^{-kappa T})^2,   T = n dt.
+    The standard error of the sample variance s^2 is sqrt((m4 - s^4) / n), m4 the sample's own
+    fourth central moment.  None of this passes through the restatement of the step."""
+    p = np.asarray(params, dtype=np.float64)
+    n = state.shape[0]
+    z = {}
+    for i, col in ((0, 1), (1, 2)):
+        v = state[:, col]
+        mean, var = cir_moments(p[5 * i], p[5 * i + 1], p[5 * i + 2], p[5 * i + 3], T)
+        c = v - v.mean()
+        s2 = np.sum(c * c) / (n - 1.0)
+        m4 = np.mean(c ** 4)
+        z[f"mean v{i + 1}"] = abs(v.mean() - mean) / np.sqrt(s2 / n)
+        z[f"var v{i + 1}"] = abs(s2 - var) / np.sqrt((m4 - s2 * s2) / n)
+    d = np.exp(-rate * T) * state[:, 0]
+    z["forward"] = abs(d.mean() - spot) / (d.std(ddof=1) / np.sqrt(n))
+    return z

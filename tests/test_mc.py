@@ -1,7 +1,9 @@
 """CPU checks of the Monte Carlo pricer: the NumPy restatement of DESIGN.md 3.15
-(tests/mc_reference.py) against Philox's known answers and against the oracle's COS prices, every
+(tests/mc_reference.py) against Philox's known answers, against the oracle's COS prices, against
+the 50-digit walk of the same step (tests/golden/mc_truth.npz) and against the CIR moments, every
 ValueError of dhcos.monte_carlo (raised before the native library is loaded), and the three new
 exports of libdhcos.so."""
+import os
 import re
 import subprocess
 
@@ -9,6 +11,7 @@ import numpy as np
 import pytest
 
 import mc_reference as R
+from conftest import GOLDEN
 from oracle import dh_oracle as O
 
 SPOT, RATE = 100.0, 0.03
@@ -58,6 +61,99 @@ def test_restatement_prices_the_model_of_the_cos_pricer():
     print(f"max |MC - COS| / stderr {z.max():.2f}; forward {zf.max():.2f}")
     assert np.all(z <= 4.0), z
     assert np.all(zf <= 4.0), zf
+
+
+# ---- the 50-digit truth fixture (tests/golden/make_mc_truth.py) -----------------------------------
+@pytest.fixture(scope="module")
+def truth():
+    with np.load(os.path.join(GOLDEN, R.TRUTH_FILE)) as z:
+        return {k: z[k] for k in z.files}
+
+
+def test_truth_fixture_is_the_configuration_the_tests_walk(truth):
+    """The fixture's pin: it holds the configuration of mc_reference.TRUTH_*, reaches every branch
+    of the step away from the switches, and its stored errors are those of its stored restatement
+    (a fresh computation: truth_errors in plain float64)."""
+    n = R.TRUTH_PATHS.size
+    assert np.array_equal(truth["paths"], R.TRUTH_PATHS) and truth["paths"].dtype == np.uint64
+    assert int(truth["seed"]) == R.TRUTH_SEED == 0x9E3779B900000005
+    assert np.array_equal(truth["sets"], R.TRUTH_SETS)
+    assert (int(truth["steps_per_year"]), tuple(truth["obs_steps"])) == (R.TRUTH_SPY, R.TRUTH_OBS)
+    assert (float(truth["spot"]), float(truth["rate"])) == (R.TRUTH_SPOT, R.TRUTH_RATE)
+    # the high words: the seed's is live, the paths' take three values and carry inside a wave
+    assert R.TRUTH_SEED >> 32 != 0
+    assert {int(p) >> 32 for p in R.TRUTH_PATHS} == {0, 1, 5}
+    assert {(1 << 32) - 1, 1 << 32} <= {int(p) for p in R.TRUTH_PATHS}
+    # the two degenerate sets are what the validation just admits
+    z, c = R.TRUTH_SETS[2], R.TRUTH_SETS[3]
+    assert z[0] == z[5] == z[10] == 0.0 and (z[4], z[9]) == (0.999, -0.999)
+    assert c[12] == 0.0 and c[10] / R.TRUTH_SPY == 1.0 and c[11] == -0.04
+    hi, lo = truth["truth"], truth["truth_lo"]
+    assert hi.shape == lo.shape == truth["restatement"].shape == (4, n, 3, 6)
+    assert np.all(np.isfinite(hi)) and np.all(np.abs(lo) <= 0.5 * np.spacing(np.abs(hi)))
+    counts = dict(zip(truth["count_names"].tolist(), truth["counts"].tolist()))
+    assert set(counts) == {"quad", "expo", "zero", "n1", "n2"} and min(counts.values()) > 0, counts
+    assert counts["quad"] + counts["expo"] == 4 * n * 8 * 2
+    assert 0 < np.sum(hi[..., 1:3] == 0.0) <= counts["zero"] <= counts["expo"]
+    assert truth["psi_gap"] > 1e-9 and truth["u_gap"] > 1e-9
+    rel, ab = R.truth_errors(truth["restatement"], hi, lo)
+    assert np.array_equal(rel, truth["rel_err"]) and np.array_equal(ab, truth["abs_err"])
+    assert os.path.getsize(os.path.join(GOLDEN, R.TRUTH_FILE)) < (1 << 16)
+
+
+def test_restatement_matches_the_50_digit_truth(truth):
+    """The NumPy restatement, run here, against the mpmath walk of the same step: 4e-15 relative on
+    all six statistics, plus 1e-15 absolute on the variances; an exact 0 of the truth (the
+    exponential branch's v' = 0) is an exact 0.  Measured where the fixture was generated: 5.5e-16
+    on S, max, min, sum; 2.7e-15 / 4.2e-15 on v1 / v2 (both at the v0 = 0 set, on variances below
+    1e-2, where the absolute 6e-17 is what counts), 2.3e-16 absolute.  exp, log, sin and cos of
+    NumPy differ in the last bit between CPUs, so the stored figures are pinned to the stored
+    restatement (test above) and this run to the bar."""
+    hi, lo = truth["truth"], truth["truth_lo"]
+    stats = R.new_stats()
+    got = R.truth_restatement(stats)
+    assert stats["psi_gap"] > 1e-9 and stats["u_gap"] > 1e-9, stats
+    counts = dict(zip(truth["count_names"].tolist(), truth["counts"].tolist()))
+    assert {k: stats[k] for k in counts} == counts        # the same decisions as the truth's
+    zero = hi == 0.0
+    assert zero.any() and not zero[..., [0, 3, 4, 5]].any()
+    assert np.all(got[zero] == 0.0) and np.all(got[~zero] != 0.0)
+    rel, ab = R.truth_errors(got, hi, lo)
+    print(f"restatement vs 50-digit truth: worst relative error (S, v1, v2, max, min, sum) {rel}; "
+          f"worst absolute error on v1, v2 {ab}; stored {truth['rel_err']}, {truth['abs_err']}")
+    bar = 4e-15 * np.abs(hi)
+    bar[..., 1:3] += 1e-15
+    d = np.abs((got - hi) - lo)
+    assert np.all(d <= bar), float(np.max(d[~zero] / bar[~zero]))
+    # the stored restatement passes the same bar: its figures are fit to scale the device's bar
+    assert np.all(np.abs((truth["restatement"] - hi) - lo) <= bar)
+
+
+@pytest.mark.parametrize("which", [0, 1])
+def test_restatement_has_the_cir_moments(which):
+    """2^16 paths, 8 steps per year, step 8, seed 0x9E3779B900000005: the sample mean and variance
+    of v1 and v2 within 4 of their standard errors of the CIR closed forms, the discounted mean of
+    S_T within 4 of its own of spot (mc_reference.moment_z_scores has the derivation).  4 is the
+    statistical bar alone."""
+    p = R.TRUTH_SETS[which]
+    state, _ = R.simulate(p, SPOT, RATE, np.arange(1 << 16), 8, 8, R.TRUTH_SEED)
+    z = R.moment_z_scores(p, state, SPOT, RATE, 1.0)
+    print(f"restatement moments, set {which}: " + ", ".join(f"{k} {v:.2f}" for k, v in z.items()))
+    assert all(v <= 4.0 for v in z.values()), z
+
+
+def test_cir_closed_forms_are_the_fixed_point_of_the_step_recursion():
+    """E[v'] = theta + (E[v] - theta) E and Var[v'] = K1 E[v] + K2 + E^2 Var[v], iterated 8 times
+    from (v0, 0), give the closed forms at T = 1 to rounding."""
+    for p in (R.README_PARAMS, R.STRESSED_PARAMS):
+        for i in (0, 1):
+            v0, kappa, theta, sigma = p[5 * i:5 * i + 4]
+            f = R.Factor(kappa, theta, sigma, 0.0, 1.0 / 8)
+            mean, var = v0, 0.0
+            for _ in range(8):
+                mean, var = theta + (mean - theta) * f.e, f.k1 * mean + f.k2 + f.e * f.e * var
+            want_m, want_v = R.cir_moments(v0, kappa, theta, sigma, 1.0)
+            assert abs(mean - want_m) <= 1e-15 * want_m and abs(var - want_v) <= 2e-15 * want_v
 
 
 # ---- every refusal of dhcos.monte_carlo, without the native library --------------------------------
