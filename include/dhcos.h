@@ -587,6 +587,62 @@ int dh_mc_price_dev(dh_ctx* ctx, const double* d_params, int64_t P, const dh_mc_
 int dh_mc_paths(dh_ctx* ctx, const double* params, int64_t P, int n_obs, const int32_t* obs_steps,
                 int64_t path0, int64_t n_paths, int steps_per_year, uint64_t seed, double* out);
 
+/* ---- American and Bermudan options by least-squares Monte Carlo (csrc/dh_lsm.h) */
+/* Early exercise on the paths of the pricer above, by the method of Longstaff and Schwartz (2001).
+ * The exercise dates are the steps e, 2 e, 3 e, ... (e = exercise_every >= 1; the start value is
+ * not a date), Delta = e / steps_per_year apart; every option's maturity step must be a whole
+ * multiple of e, option j has D_j = step_j / e dates and date D_j is its maturity.  The state
+ * (S, v1, v2) of every path is stored at every date; the dates are then walked backwards, one
+ * launch each: at date d < D_j the discounted realised cashflow Y = e^{-r Delta} cash of the paths
+ * in the money (intrinsic value h > 0) is regressed on the DH_LSM_BASIS terms
+ *     1, x, y1, y2, x^2, y1^2, y2^2, x y1, x y2, y1 y2,   x = S / K - 1, y_i = v_i / theta_i - 1,
+ * by the normal equations (Cholesky without pivoting), and a path exercises (cash = h, its
+ * exercise date = d) where h > 0 and h > the fitted value, else cash = Y.  Nobody exercises at a
+ * date with fewer than DH_LSM_MIN_ITM paths in the money or a Cholesky pivot that is not > 0: its
+ * coefficient row is ten NaNs.  The same paths fit and value the policy (in-sample).  No atomics,
+ * every sum in a fixed order: results are a function of the arguments alone.                     */
+enum {
+    DH_LSM_MAX_OPTIONS = 16,     /* options of one call (all priced from the same paths) */
+    DH_LSM_BASIS = 10,           /* regression terms */
+    DH_LSM_MIN_ITM = 64,         /* in-the-money paths a date needs to be fitted */
+    DH_LSM_SLOTS = 128,          /* blocks per (set, option) of a backward launch at most; a block
+                                    walks the chunks of 256 paths slot, slot + slots, ... */
+    DH_LSM_MAX_GIB = 16          /* cap of the path store, P n_paths (24 Dmax + 12 n_options) bytes */
+};
+typedef struct {
+    int32_t is_call;             /* 0 put, else call */
+    int32_t pad;                 /* not read */
+    double strike;               /* finite, >= 0 */
+    double maturity;             /* years: a whole number n >= 1 of steps (to 1e-9 relative), n a
+                                    multiple of exercise_every */
+} dh_lsm_option;
+/* price[p * n_options + j] = e^{-r Delta} mean of the cashflows of option j under params[p] after
+ * date 1, stderr their sample standard error (dh_mc_price's formula); european / european_stderr
+ * the same of the maturity payoffs of the same paths, discounted by e^{-r T} with T = D_j Delta
+ * (price - european is the early-exercise premium; european is dh_mc_price's European value of the
+ * same seed, paths and steps up to the order of its sum).  coef (may be NULL) is
+ * [P][n_options][Dmax][DH_LSM_BASIS], Dmax the largest D_j: row d - 1 holds the coefficients used
+ * at date d, NaN where the date was skipped, at the option's maturity date and past it.
+ * exercise_date (may be NULL) is [P][n_options][n_paths]: the date 1 .. D_j at which each path's
+ * cashflow falls (D_j where it never exercised early).  Host arrays, synchronous.  DH_E_ARG,
+ * before any device work and naming the argument in dh_last_error(): the parameter, n_paths,
+ * steps_per_year, P, strike and maturity cases of dh_mc_price; exercise_every < 1; a maturity step
+ * that is not a multiple of exercise_every; n_options outside [1, DH_LSM_MAX_OPTIONS]; a path
+ * store above DH_LSM_MAX_GIB GiB (ask for fewer paths or parameter sets per call).              */
+int dh_lsm_price(dh_ctx* ctx, const double* params, int64_t P, const dh_lsm_option* options,
+                 int n_options, int64_t n_paths, int steps_per_year, int exercise_every,
+                 uint64_t seed, double* price, double* stderr_out, double* european,
+                 double* european_stderr, double* coef, int32_t* exercise_date);
+/* The same over device pointers (`options` stays a host array, copied when the call returns; d_coef
+ * and d_exercise_date may be NULL): 2 + Dmax launches enqueued on `stream` (hipStream_t; NULL = the
+ * context's), no synchronisation, no allocation after warm-up.  The parameter values are the
+ * caller's promise (not readable here); the same bits as dh_lsm_price.                          */
+int dh_lsm_price_dev(dh_ctx* ctx, const double* d_params, int64_t P, const dh_lsm_option* options,
+                     int n_options, int64_t n_paths, int steps_per_year, int exercise_every,
+                     uint64_t seed, double* d_price, double* d_stderr, double* d_european,
+                     double* d_european_stderr, double* d_coef, int32_t* d_exercise_date,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,10 @@ struct dh_ctx {
     // the Monte Carlo pricer (dh_mc.h): staged records, sorted options / observation steps, the
     // blocks' partial sums, staged outputs
     DevBuf mc_params, mc_opts, mc_part, mc_out;
+    // the least-squares Monte Carlo pricer (dh_lsm.h): the states at the exercise dates, each
+    // option's cashflow and exercise date per path, the blocks' normal-equation and price
+    // partials, options, per-set discounts, coefficients, staged outputs
+    DevBuf lsm_state, lsm_cash, lsm_tau, lsm_part, lsm_fin, lsm_opts, lsm_disc, lsm_coef, lsm_out;
 };
 
 struct dh_surface {

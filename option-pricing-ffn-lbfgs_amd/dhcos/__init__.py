@@ -9,6 +9,7 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
     implied_vol                       (new: Black-Scholes implied volatility of prices)
     calibrate_batch                   (new: many markets on one option grid, calibrated together)
     monte_carlo                       (new: path pricing of European, Asian and barrier options)
+    american_monte_carlo              (new: American and Bermudan options by least-squares Monte Carlo)
 
 All pricing arithmetic runs in libdhcos.so (hand-written gfx950 HIP kernels, C-ABI in
 include/dhcos.h); the native library is loaded on first use and there is no CPU fallback.
@@ -21,9 +22,11 @@ from .calibrator import CalibrationResult, DoubleHestonJumpCalibrator
 from .generator import generate_synthetic_calibrations
 from .batch import BatchCalibrationResult, calibrate_batch
 from .montecarlo import MonteCarloResult, monte_carlo
+from .american import AmericanMonteCarloResult, american_monte_carlo
 from ._native import NativeError
 
 __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
            "generate_synthetic_calibrations", "implied_vol", "NativeError", "calibrate_batch",
-           "BatchCalibrationResult", "monte_carlo", "MonteCarloResult"]
+           "BatchCalibrationResult", "monte_carlo", "MonteCarloResult",
+           "american_monte_carlo", "AmericanMonteCarloResult"]
 __version__ = "0.1.0"

@@ -34,6 +34,11 @@ COMM_ID_BYTES = 128
 MC_KINDS = {"european": 0, "asian": 1, "up_and_out": 2, "down_and_out": 3}   # DH_MC_*
 MC_MAX_OPTIONS = 64            # DH_MC_MAX_OPTIONS
 MC_POISSON_CAP = 16            # DH_MC_POISSON_CAP
+LSM_MAX_OPTIONS = 16           # DH_LSM_MAX_OPTIONS
+LSM_BASIS = 10                 # DH_LSM_BASIS: regression terms
+LSM_MIN_ITM = 64               # DH_LSM_MIN_ITM: in-the-money paths a date needs to be fitted
+LSM_SLOTS = 128                # DH_LSM_SLOTS: blocks per (set, option) of a backward launch
+LSM_MAX_GIB = 16               # DH_LSM_MAX_GIB: cap of the path store
 STAMPS_PER_BLOCK = 32          # kStamps of the DH_STAMPS build (csrc/dh_kernels.hip)
 
 _dp = C.POINTER(C.c_double)
@@ -64,8 +69,15 @@ class McOption(C.Structure):
                 ("maturity", C.c_double), ("barrier", C.c_double)]
 
 
+class LsmOption(C.Structure):
+    """dh_lsm_option (include/dhcos.h): one American / Bermudan option of dh_lsm_price."""
+    _fields_ = [("is_call", C.c_int32), ("pad", C.c_int32), ("strike", C.c_double),
+                ("maturity", C.c_double)]
+
+
 _int, _i64, _dbl = C.c_int, C.c_int64, C.c_double          # the header's int, int64_t, double
 _lbo, _lbr, _mco = C.POINTER(LbOptions), C.POINTER(LbResult), C.POINTER(McOption)
+_lso = C.POINTER(LsmOption)
 
 # name -> (restype, argtypes); mirrors include/dhcos.h one to one, in its order
 SIGNATURES = {
@@ -172,6 +184,11 @@ SIGNATURES = {
     "dh_mc_price_dev": (_int, [_vp, _vp, _i64, _mco, _int, _i64, _int, C.c_uint64, _vp, _vp,
                                _vp]),
     "dh_mc_paths": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _i64, _int, C.c_uint64, _vp]),
+    # ---- American and Bermudan options by least-squares Monte Carlo
+    "dh_lsm_price": (_int, [_vp, _vp, _i64, _lso, _int, _i64, _int, _int, C.c_uint64, _vp, _vp,
+                            _vp, _vp, _vp, _vp]),
+    "dh_lsm_price_dev": (_int, [_vp, _vp, _i64, _lso, _int, _i64, _int, _int, C.c_uint64, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -556,6 +573,50 @@ class Context(_Handle):
                                       obs.ctypes.data, int(path0), int(n_paths),
                                       int(steps_per_year), int(seed), out.ctypes.data))
         return out
+
+    def lsm_price(self, records, options, dates, n_paths, steps_per_year, exercise_every, seed,
+                  policy=False):
+        """dh_lsm_price: records [P, 16], options an array of LsmOption, dates the largest number
+        of exercise dates of an option -> (price, stderr, european, european_stderr), each
+        [P, n_options], then coefficients [P, n_options, dates, LSM_BASIS] and exercise_date int32
+        [P, n_options, n_paths], both None unless ``policy``."""
+        rec = _records(records)
+        P, n_opt = rec.shape[0], len(options)
+        out = np.empty((4, P, n_opt))
+        coef = np.empty((P, n_opt, int(dates), LSM_BASIS)) if policy else None
+        tau = np.empty((P, n_opt, int(n_paths)), dtype=np.int32) if policy else None
+        with self._lock:
+            _check(load().dh_lsm_price(self._h, rec.ctypes.data, P, options, n_opt, int(n_paths),
+                                       int(steps_per_year), int(exercise_every), int(seed),
+                                       *(o.ctypes.data for o in out), _addr(coef), _addr(tau)))
+        return out[0], out[1], out[2], out[3], coef, tau
+
+    def lsm_price_dev(self, records, options, dates, n_paths, steps_per_year, exercise_every,
+                      seed, policy=False, stream=None):
+        """dh_lsm_price_dev: records a contiguous float64 [P, 16] torch tensor on this context's
+        device -> the tensors of ``lsm_price``, enqueued on ``stream`` (None: the context's own;
+        the null stream cannot be named, as mc_price_dev) without synchronisation."""
+        import torch
+        if (records.dtype != torch.float64 or not records.is_contiguous() or records.dim() != 2
+                or records.shape[1] != PARAM_STRIDE or not records.is_cuda
+                or records.device.index != self.device):
+            raise ValueError(f"lsm_price_dev: a contiguous float64 [P, {PARAM_STRIDE}] tensor on "
+                             f"cuda:{self.device}")
+        P, n_opt = records.shape[0], len(options)
+        out = torch.empty((4, P, n_opt), dtype=torch.float64, device=records.device)
+        coef = tau = None
+        if policy:
+            coef = torch.empty((P, n_opt, int(dates), LSM_BASIS), dtype=torch.float64,
+                               device=records.device)
+            tau = torch.empty((P, n_opt, int(n_paths)), dtype=torch.int32, device=records.device)
+        st = _stream_handle("lsm_price_dev", stream)
+        with self._lock:
+            _check(load().dh_lsm_price_dev(
+                self._h, records.data_ptr(), P, options, n_opt, int(n_paths), int(steps_per_year),
+                int(exercise_every), int(seed), *(o.data_ptr() for o in out),
+                None if coef is None else coef.data_ptr(),
+                None if tau is None else tau.data_ptr(), _addr(st)))
+        return out[0], out[1], out[2], out[3], coef, tau
 
     def implied_vol_dev(self, price, S0, K, T, r, q, is_call, out=None, stream=None):
         """dh_implied_vol_dev over torch tensors on this context's device: float64 price, S0, K,
@@ -1444,7 +1505,7 @@ def default_context(device: int | None = None) -> Context:
 
 
 # every public top-level name, in SIGNATURES' groups: the library, context and surfaces, L-BFGS-B,
-# generator, communicator, Monte Carlo
+# generator, communicator, Monte Carlo, least-squares Monte Carlo
 __all__ = [
     "LIB_PATH", "SIGNATURES", "NativeError", "load", "runtime_shared_with_torch", "device_count",
     "resolve_device", "default_context", "PARAM_STRIDE", "MAX_N", "MAX_N_PER_TERM",
@@ -1457,4 +1518,5 @@ __all__ = [
     "MATH_PROBE_FNS", "math_probe",
     "COMM_ID_BYTES", "Comm", "comm_id", "best_start",
     "McOption", "MC_KINDS", "MC_MAX_OPTIONS", "MC_POISSON_CAP",
+    "LsmOption", "LSM_MAX_OPTIONS", "LSM_BASIS", "LSM_MIN_ITM", "LSM_SLOTS", "LSM_MAX_GIB",
 ]

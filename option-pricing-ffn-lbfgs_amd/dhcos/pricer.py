@@ -138,6 +138,20 @@ class DoubleHeston:
                           device=self.device)
         return np.float64(res.price[0]), np.float64(res.stderr[0])
 
+    def american_monte_carlo(self, n_paths=1 << 17, steps_per_year=64, exercise_every=1, seed=0):
+        """(price, stderr) of this instance's option with early exercise at every
+        ``exercise_every``-th step, by least-squares Monte Carlo (``dhcos.american_monte_carlo``;
+        q must be 0, the simulated dynamics carry no dividend yield)."""
+        from .american import american_monte_carlo
+        if self.q != 0.0:
+            raise ValueError("american_monte_carlo: the simulated dynamics have q = 0")
+        res = american_monte_carlo([getattr(self, f) for f in MODEL_FIELDS], self.S0, self.r,
+                                   [{"strike": self.K, "maturity": self.T,
+                                     "option_type": self.option_type}],
+                                   n_paths=n_paths, steps_per_year=steps_per_year,
+                                   exercise_every=exercise_every, seed=seed, device=self.device)
+        return np.float64(res.price[0]), np.float64(res.stderr[0])
+
     # -- batched entry point ----------------------------------------------------------------
     @staticmethod
     def price_batch(params, S0, K, T, r, option_type="C", N=128, q=0.0, L=10.0, device=None):
