@@ -587,6 +587,51 @@ int dh_mc_price_dev(dh_ctx* ctx, const double* d_params, int64_t P, const dh_mc_
 int dh_mc_paths(dh_ctx* ctx, const double* params, int64_t P, int n_obs, const int32_t* obs_steps,
                 int64_t path0, int64_t n_paths, int steps_per_year, uint64_t seed, double* out);
 
+/* ---- Variance reduction for the path pricer (csrc/dh_mc_vr.h) ------------- */
+/* Antithetic pairs and one control variate per option, by flag.
+ * Mirror: the mirror of path i uses path i's Philox words, the uniforms 1 - U (exact: U is an odd
+ * multiple of 2^-53) and the normals -Z; everything else is the step of 3.15.  Under
+ * DH_MC_VR_ANTITHETIC n_paths counts walks (even, >= 4), there are n = n_paths / 2 pairs and the
+ * sample y_i is the average of the payoffs of path i and its mirror; else n = n_paths, y_i the
+ * payoff of path i.  Under DH_MC_VR_CONTROL the control c_i of a european option, and of any
+ * option with strike 0, is S at its maturity step (known discounted mean m = S0); of an asian,
+ * up_and_out or down_and_out option it is the European payoff of the same type and strike at the
+ * same step, whose mean m is its COS price (dh_surface_price_dev, N = DH_MC_VR_COS_N, L =
+ * DH_MC_VR_COS_L, the set's spot and rate, q = 0); under both flags c_i is the pair's average.
+ * With the five sums over the n samples, every one in dh_mc_price's order, and disc = e^{-rT}:
+ *     Cyy = Syy - Sy Sy / n,  Ccc = Scc - Sc Sc / n,  Cyc = Syc - Sy Sc / n,
+ *     beta = Ccc > 0 ? Cyc / Ccc : 0,
+ *     base_price = disc Sy / n,  base_stderr = disc sqrt(max(Cyy, 0) / (n (n - 1))),
+ *     price = base_price - beta (disc Sc / n - m),
+ *     stderr = disc sqrt(max(Cyy - beta Cyc, 0) / (n (n - 1))).
+ * Without the control flag beta = 0, m = NaN, price = base_price, stderr = base_stderr; without
+ * the antithetic flag base_price / base_stderr are dh_mc_price's bits.  beta is fitted on the
+ * priced sample: the estimator carries the usual O(1 / n) bias, which is not corrected.         */
+enum dh_mc_vr_flag { DH_MC_VR_ANTITHETIC = 1, DH_MC_VR_CONTROL = 2 };
+enum dh_mc_vr_cos { DH_MC_VR_COS_N = 256 };   /* series length of the control means */
+#define DH_MC_VR_COS_L (10.0)                 /* and their truncation width */
+/* Host arrays [P][n_options], synchronous; base_price, base_stderr, beta and control_mean may be
+ * NULL.  DH_E_ARG before any device work: everything dh_mc_price refuses; flags == 0 (that is
+ * dh_mc_price) or with unknown bits; under the antithetic flag an odd n_paths or n_paths < 4.   */
+int dh_mc_price_vr(dh_ctx* ctx, const double* params, int64_t P, const dh_mc_option* options,
+                   int n_options, int64_t n_paths, int steps_per_year, uint64_t seed, int flags,
+                   double* price, double* stderr_out, double* base_price, double* base_stderr,
+                   double* beta, double* control_mean);
+/* The same over device pointers (as dh_mc_price_dev; the last four may be NULL): enqueued on
+ * `stream` without synchronisation, the same bits as dh_mc_price_vr.  The twins' option surface is
+ * kept in the context: a call whose twins (strike, maturity, type, in maturity order) are those of
+ * the call before rebuilds nothing; one whose twins differ waits for the earlier call's stream,
+ * then builds its surface (one allocation, one blocking copy).                                  */
+int dh_mc_price_vr_dev(dh_ctx* ctx, const double* d_params, int64_t P, const dh_mc_option* options,
+                       int n_options, int64_t n_paths, int steps_per_year, uint64_t seed, int flags,
+                       double* d_price, double* d_stderr, double* d_base_price,
+                       double* d_base_stderr, double* d_beta, double* d_control_mean, void* stream);
+/* dh_mc_paths with a mirror switch: mirror != 0 gives the statistics of the mirrors of the paths,
+ * by the pair step the antithetic kernel runs; mirror == 0 is dh_mc_paths, bit for bit.         */
+int dh_mc_paths_vr(dh_ctx* ctx, const double* params, int64_t P, int n_obs,
+                   const int32_t* obs_steps, int64_t path0, int64_t n_paths, int steps_per_year,
+                   uint64_t seed, int mirror, double* out);
+
 /* ---- American and Bermudan options by least-squares Monte Carlo (csrc/dh_lsm.h) */
 /* Early exercise on the paths of the pricer above, by the method of Longstaff and Schwartz (2001).
  * The exercise dates are the steps e, 2 e, 3 e, ... (e = exercise_every >= 1; the start value is

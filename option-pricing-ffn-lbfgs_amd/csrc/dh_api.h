@@ -60,6 +60,7 @@ int dh_ctx_destroy(dh_ctx* ctx) {
     for (hipEvent_t e : ctx->lb_ev)
         if (e) (void)hipEventDestroy(e);
     gen_bufs_release(ctx);
+    if (ctx->vr_surf) (void)dh_surface_destroy(ctx->vr_surf);
     for (auto& F : ctx->fg)
         if (F.done) (void)hipEventDestroy(F.done);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -166,6 +166,13 @@ struct dh_ctx {
     // the Monte Carlo pricer (dh_mc.h): staged records, sorted options / observation steps, the
     // blocks' partial sums, staged outputs
     DevBuf mc_params, mc_opts, mc_part, mc_out;
+    // its variance reduction (dh_mc_vr.h): the blocks' five partial sums, the records with q
+    // zeroed, the twins' COS prices; the twins' surface, the (strike, maturity, type) list it was
+    // built from and the stream of the last call that read it
+    DevBuf mc_vr_part, mc_vr_rec, mc_vr_cos;
+    dh_surface* vr_surf = nullptr;
+    std::vector<double> vr_key;
+    hipStream_t vr_stream = nullptr;
     // the least-squares Monte Carlo pricer (dh_lsm.h): the states at the exercise dates, each
     // option's cashflow and exercise date per path, the blocks' normal-equation and price
     // partials, options, per-set discounts, coefficients, staged outputs

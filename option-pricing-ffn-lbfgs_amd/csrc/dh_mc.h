@@ -384,6 +384,30 @@ int check_options(const dh_mc_option* options, int n_options, int steps_per_year
     return DH_OK;
 }
 
+// the arguments of dh_mc_paths (and of dh_mc_paths_vr, dh_mc_vr.h)
+int check_paths(const dh_ctx* ctx, const double* params, int64_t P, int n_obs,
+                const int32_t* obs_steps, int64_t path0, int64_t n_paths, int steps_per_year,
+                const double* out) {
+    int rc = check_common(ctx, P, steps_per_year);
+    if (rc) return rc;
+    if (!params || !out) return fail(DH_E_ARG, "null argument");
+    rc = check_params(params, P, steps_per_year);
+    if (rc) return rc;
+    if (n_obs < 1 || !obs_steps) return fail(DH_E_ARG, "n_obs must be >= 1 and obs_steps given");
+    for (int j = 0; j < n_obs; ++j)
+        if (obs_steps[j] < 1 || (j > 0 && obs_steps[j] <= obs_steps[j - 1]))
+            return fail(DH_E_ARG, "obs_steps must be >= 1 and strictly increasing (entry " +
+                                      std::to_string(j) + ")");
+    if (path0 < 0) return fail(DH_E_ARG, "path0 must be >= 0");
+    if (n_paths < 1 || n_paths > (int64_t(1) << 31) * kThreads || path0 > INT64_MAX - n_paths)
+        return fail(DH_E_ARG, "n_paths must be >= 1 and path0 + n_paths fit 63 bits, got " +
+                                  std::to_string(n_paths));
+    if ((double)P * (double)n_paths * (double)n_obs * 6.0 > 0x1p31)
+        return fail(DH_E_ARG, "out [P, n_paths, n_obs, 6] is larger than 2^31 doubles: ask for "
+                              "fewer paths per call (path0 selects the range)");
+    return DH_OK;
+}
+
 }  // namespace dhmc
 
 extern "C" int dh_mc_price_dev(dh_ctx* ctx, const double* d_params, int64_t P,
@@ -456,25 +480,10 @@ extern "C" int dh_mc_price(dh_ctx* ctx, const double* params, int64_t P,
 extern "C" int dh_mc_paths(dh_ctx* ctx, const double* params, int64_t P, int n_obs,
                            const int32_t* obs_steps, int64_t path0, int64_t n_paths,
                            int steps_per_year, uint64_t seed, double* out) {
-    int rc = dhmc::check_common(ctx, P, steps_per_year);
+    const int rc = dhmc::check_paths(ctx, params, P, n_obs, obs_steps, path0, n_paths,
+                                     steps_per_year, out);
     if (rc) return rc;
-    if (!params || !out) return fail(DH_E_ARG, "null argument");
-    rc = dhmc::check_params(params, P, steps_per_year);
-    if (rc) return rc;
-    if (n_obs < 1 || !obs_steps) return fail(DH_E_ARG, "n_obs must be >= 1 and obs_steps given");
-    for (int j = 0; j < n_obs; ++j)
-        if (obs_steps[j] < 1 || (j > 0 && obs_steps[j] <= obs_steps[j - 1]))
-            return fail(DH_E_ARG, "obs_steps must be >= 1 and strictly increasing (entry " +
-                                      std::to_string(j) + ")");
-    if (path0 < 0) return fail(DH_E_ARG, "path0 must be >= 0");
-    if (n_paths < 1 || n_paths > (int64_t(1) << 31) * dhmc::kThreads ||
-        path0 > INT64_MAX - n_paths)
-        return fail(DH_E_ARG, "n_paths must be >= 1 and path0 + n_paths fit 63 bits, got " +
-                                  std::to_string(n_paths));
     const double words = (double)P * (double)n_paths * (double)n_obs * 6.0;
-    if (words > 0x1p31)
-        return fail(DH_E_ARG, "out [P, n_paths, n_obs, 6] is larger than 2^31 doubles: ask for "
-                              "fewer paths per call (path0 selects the range)");
     DeviceScope dev_scope(ctx->device);
     if (dev_scope.rc) return dev_scope.rc;
     const size_t pb = (size_t)P * DH_PARAM_STRIDE * 8, sb = (size_t)n_obs * 4;

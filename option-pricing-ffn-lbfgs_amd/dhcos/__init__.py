@@ -8,7 +8,8 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
     generate_synthetic_calibrations   src/data/synthetic_generator.py
     implied_vol                       (new: Black-Scholes implied volatility of prices)
     calibrate_batch                   (new: many markets on one option grid, calibrated together)
-    monte_carlo                       (new: path pricing of European, Asian and barrier options)
+    monte_carlo                       (new: path pricing of European, Asian and barrier options,
+                                       with antithetic pairs and COS-priced control variates)
     american_monte_carlo              (new: American and Bermudan options by least-squares Monte Carlo)
 
 All pricing arithmetic runs in libdhcos.so (hand-written gfx950 HIP kernels, C-ABI in
@@ -21,12 +22,13 @@ from .pricer import DoubleHeston, implied_vol
 from .calibrator import CalibrationResult, DoubleHestonJumpCalibrator
 from .generator import generate_synthetic_calibrations
 from .batch import BatchCalibrationResult, calibrate_batch
-from .montecarlo import MonteCarloResult, monte_carlo
+from .montecarlo import MonteCarloResult, VarianceReducedResult, monte_carlo
 from .american import AmericanMonteCarloResult, american_monte_carlo
 from ._native import NativeError
 
 __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
            "generate_synthetic_calibrations", "implied_vol", "NativeError", "calibrate_batch",
            "BatchCalibrationResult", "monte_carlo", "MonteCarloResult",
+           "VarianceReducedResult",
            "american_monte_carlo", "AmericanMonteCarloResult"]
 __version__ = "0.1.0"

@@ -34,6 +34,8 @@ COMM_ID_BYTES = 128
 MC_KINDS = {"european": 0, "asian": 1, "up_and_out": 2, "down_and_out": 3}   # DH_MC_*
 MC_MAX_OPTIONS = 64            # DH_MC_MAX_OPTIONS
 MC_POISSON_CAP = 16            # DH_MC_POISSON_CAP
+MC_VR_ANTITHETIC, MC_VR_CONTROL = 1, 2     # DH_MC_VR_*: the flags of dh_mc_price_vr
+MC_VR_COS_N, MC_VR_COS_L = 256, 10.0       # DH_MC_VR_COS_*: the COS series of the control means
 LSM_MAX_OPTIONS = 16           # DH_LSM_MAX_OPTIONS
 LSM_BASIS = 10                 # DH_LSM_BASIS: regression terms
 LSM_MIN_ITM = 64               # DH_LSM_MIN_ITM: in-the-money paths a date needs to be fitted
@@ -184,6 +186,13 @@ SIGNATURES = {
     "dh_mc_price_dev": (_int, [_vp, _vp, _i64, _mco, _int, _i64, _int, C.c_uint64, _vp, _vp,
                                _vp]),
     "dh_mc_paths": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _i64, _int, C.c_uint64, _vp]),
+    # ---- its antithetic pairs and control variates
+    "dh_mc_price_vr": (_int, [_vp, _vp, _i64, _mco, _int, _i64, _int, C.c_uint64, _int, _vp, _vp,
+                              _vp, _vp, _vp, _vp]),
+    "dh_mc_price_vr_dev": (_int, [_vp, _vp, _i64, _mco, _int, _i64, _int, C.c_uint64, _int, _vp,
+                                  _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dh_mc_paths_vr": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _i64, _int, C.c_uint64, _int,
+                              _vp]),
     # ---- American and Bermudan options by least-squares Monte Carlo
     "dh_lsm_price": (_int, [_vp, _vp, _i64, _lso, _int, _i64, _int, _int, C.c_uint64, _vp, _vp,
                             _vp, _vp, _vp, _vp]),
@@ -572,6 +581,49 @@ class Context(_Handle):
             _check(load().dh_mc_paths(self._h, rec.ctypes.data, rec.shape[0], obs.size,
                                       obs.ctypes.data, int(path0), int(n_paths),
                                       int(steps_per_year), int(seed), out.ctypes.data))
+        return out
+
+    def mc_price_vr(self, records, options, n_paths, steps_per_year, seed, flags):
+        """dh_mc_price_vr: records [P, 16], options an array of McOption, flags of MC_VR_* ->
+        (price, stderr, base_price, base_stderr, beta, control_mean), each [P, n_options]."""
+        rec = _records(records)
+        P, n_opt = rec.shape[0], len(options)
+        out = np.empty((6, P, n_opt))
+        with self._lock:
+            _check(load().dh_mc_price_vr(self._h, rec.ctypes.data, P, options, n_opt,
+                                         int(n_paths), int(steps_per_year), int(seed), int(flags),
+                                         *(o.ctypes.data for o in out)))
+        return tuple(out)
+
+    def mc_price_vr_dev(self, records, options, n_paths, steps_per_year, seed, flags, stream=None):
+        """dh_mc_price_vr_dev: records a contiguous float64 [P, 16] torch tensor on this context's
+        device -> the six tensors of ``mc_price_vr``, enqueued on ``stream`` (None: the context's
+        own; the null stream cannot be named, as mc_price_dev) without synchronisation."""
+        import torch
+        if (records.dtype != torch.float64 or not records.is_contiguous() or records.dim() != 2
+                or records.shape[1] != PARAM_STRIDE or not records.is_cuda
+                or records.device.index != self.device):
+            raise ValueError(f"mc_price_vr_dev: a contiguous float64 [P, {PARAM_STRIDE}] tensor "
+                             f"on cuda:{self.device}")
+        P, n_opt = records.shape[0], len(options)
+        out = torch.empty((6, P, n_opt), dtype=torch.float64, device=records.device)
+        st = _stream_handle("mc_price_vr_dev", stream)
+        with self._lock:
+            _check(load().dh_mc_price_vr_dev(self._h, records.data_ptr(), P, options, n_opt,
+                                             int(n_paths), int(steps_per_year), int(seed),
+                                             int(flags), *(o.data_ptr() for o in out), _addr(st)))
+        return tuple(out)
+
+    def mc_paths_vr(self, records, obs_steps, path0, n_paths, steps_per_year, seed, mirror):
+        """dh_mc_paths_vr: ``mc_paths`` of the paths' mirrors (``mirror``), or of the paths."""
+        rec = _records(records)
+        obs = np.ascontiguousarray(obs_steps, dtype=np.int32).reshape(-1)
+        out = np.empty((rec.shape[0], int(n_paths), obs.size, 6))
+        with self._lock:
+            _check(load().dh_mc_paths_vr(self._h, rec.ctypes.data, rec.shape[0], obs.size,
+                                         obs.ctypes.data, int(path0), int(n_paths),
+                                         int(steps_per_year), int(seed), 1 if mirror else 0,
+                                         out.ctypes.data))
         return out
 
     def lsm_price(self, records, options, dates, n_paths, steps_per_year, exercise_every, seed,
@@ -1518,5 +1570,6 @@ __all__ = [
     "MATH_PROBE_FNS", "math_probe",
     "COMM_ID_BYTES", "Comm", "comm_id", "best_start",
     "McOption", "MC_KINDS", "MC_MAX_OPTIONS", "MC_POISSON_CAP",
+    "MC_VR_ANTITHETIC", "MC_VR_CONTROL", "MC_VR_COS_N", "MC_VR_COS_L",
     "LsmOption", "LSM_MAX_OPTIONS", "LSM_BASIS", "LSM_MIN_ITM", "LSM_SLOTS", "LSM_MAX_GIB",
 ]

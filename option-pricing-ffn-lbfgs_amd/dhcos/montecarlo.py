@@ -37,6 +37,40 @@ class MonteCarloResult:
         return self.price - z * self.stderr, self.price + z * self.stderr
 
 
+@dataclass
+class VarianceReducedResult(MonteCarloResult):
+    """``monte_carlo`` with ``antithetic`` and / or ``control_variate`` (dh_mc_price_vr, DESIGN.md
+    3.15.2).  ``price`` / ``stderr`` are the reduced estimator's; ``base_price`` / ``base_stderr``
+    the plain mean of the same samples (pair averages under ``antithetic``); ``beta`` the fitted
+    control coefficient (0 without a control) and ``control_mean`` the control's known mean: spot
+    for Europeans and strike-0 options, else the COS price of the option's European twin (NaN
+    without a control).  ``n_paths`` counts walks: ``n_paths / 2`` pairs under ``antithetic``.
+    beta is fitted on the priced sample, so ``price`` carries the usual O(1 / n) bias."""
+    base_price: np.ndarray = None
+    base_stderr: np.ndarray = None
+    beta: np.ndarray = None
+    control_mean: np.ndarray = None
+    antithetic: bool = False
+    control_variate: bool = False
+
+    @property
+    def variance_ratio(self):
+        """(base_stderr / stderr)^2: the variance the control removed from the same samples (inf
+        where the control is the payoff itself, NaN where both errors are 0)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (self.base_stderr / self.stderr) ** 2
+
+
+def _vr_flags(antithetic, control_variate, n_paths):
+    """The DH_MC_VR_* flags of the two keywords, 0 for the plain pricer."""
+    flags = (_native.MC_VR_ANTITHETIC if antithetic else 0) \
+        | (_native.MC_VR_CONTROL if control_variate else 0)
+    if antithetic and (n_paths % 2 or n_paths < 4):
+        raise ValueError(f"n_paths: counts walks, so with antithetic=True an even number >= 4, "
+                         f"got {n_paths!r}")
+    return flags
+
+
 def _records(parameters, spot, risk_free):
     """-> ([P, 16] records, True if `parameters` was one set)."""
     if isinstance(parameters, dict):
@@ -129,7 +163,8 @@ def _options(options, steps_per_year):
 
 
 def monte_carlo(parameters, spot, risk_free, options, *, n_paths=1 << 20, steps_per_year=64,
-                seed=0, device=None) -> MonteCarloResult:
+                seed=0, device=None, antithetic=False,
+                control_variate=False) -> MonteCarloResult:
     """Price ``options`` by simulating the model's SDE on the GPU.
 
     parameters: a dict of the 13 names, a ``[13]`` array or ``[P, 13]`` (what
@@ -138,27 +173,43 @@ def monte_carlo(parameters, spot, risk_free, options, *, n_paths=1 << 20, steps_
     ``option_type``) with optional ``kind`` (``"european"``, ``"asian"``, ``"up_and_out"``,
     ``"down_and_out"``) and ``barrier``.  Every maturity must be a whole number of steps of
     ``1 / steps_per_year``; barriers and averages are monitored at every step date.  All parameter
-    sets see the same random numbers, and the same call gives the same bits."""
+    sets see the same random numbers, and the same call gives the same bits.
+
+    antithetic: walk every path together with its mirror (the same random words, ``1 - U`` and
+    ``-Z``) and average the two payoffs; ``n_paths`` counts walks and must be even and >= 4.
+    control_variate: subtract ``beta`` times a control's deviation from its known mean -- the
+    discounted terminal spot for Europeans, the COS price of the European twin for Asians and
+    barriers.  With either keyword the result is a ``VarianceReducedResult``; with neither the call
+    is the plain pricer's, unchanged."""
     steps_per_year = _check_steps_per_year(steps_per_year)
     seed = _check_seed(seed)
     if int(n_paths) != n_paths or n_paths < 2:
         raise ValueError(f"n_paths: a whole number >= 2, got {n_paths!r}")
+    flags = _vr_flags(antithetic, control_variate, int(n_paths))
     rec, single = _records(parameters, spot, risk_free)
     _check_records(rec, steps_per_year)
     opts = _options(options, steps_per_year)
-    price, err = _native.default_context(device).mc_price(rec, opts, int(n_paths), steps_per_year,
-                                                          seed)
+    if not flags:
+        price, err = _native.default_context(device).mc_price(rec, opts, int(n_paths),
+                                                              steps_per_year, seed)
+        if single:
+            price, err = price[0], err[0]
+        return MonteCarloResult(price, err, int(n_paths), steps_per_year, seed)
+    out = _native.default_context(device).mc_price_vr(rec, opts, int(n_paths), steps_per_year,
+                                                      seed, flags)
     if single:
-        price, err = price[0], err[0]
-    return MonteCarloResult(price, err, int(n_paths), steps_per_year, seed)
+        out = tuple(a[0] for a in out)
+    return VarianceReducedResult(out[0], out[1], int(n_paths), steps_per_year, seed, *out[2:],
+                                 bool(antithetic), bool(control_variate))
 
 
 def simulate_paths(parameters, spot, risk_free, obs_steps, *, n_paths, path0=0, steps_per_year=64,
-                   seed=0, device=None) -> np.ndarray:
+                   seed=0, device=None, mirror=False) -> np.ndarray:
     """dh_mc_paths: ``S, v1, v2, running max, running min, running sum`` of paths ``path0 ..
     path0 + n_paths - 1`` at the listed steps (>= 1, strictly increasing), by the pricing kernel's
     own step function -> ``[n_paths, n_obs, 6]``, or ``[P, n_paths, n_obs, 6]`` for ``[P, 13]``
-    parameters."""
+    parameters.  mirror: the statistics of the paths' antithetic mirrors instead
+    (dh_mc_paths_vr)."""
     steps_per_year = _check_steps_per_year(steps_per_year)
     seed = _check_seed(seed)
     if int(n_paths) != n_paths or n_paths < 1:
@@ -175,9 +226,15 @@ def simulate_paths(parameters, spot, risk_free, obs_steps, *, n_paths, path0=0, 
     if rec.shape[0] * int(n_paths) * obs.size * 6 > 1 << 31:
         raise ValueError("simulate_paths: more than 2^31 doubles of output; ask for fewer paths "
                          "per call (path0 selects the range)")
-    out = _native.default_context(device).mc_paths(rec, obs.astype(np.int32), int(path0),
-                                                   int(n_paths), steps_per_year, seed)
+    ctx = _native.default_context(device)
+    if mirror:
+        out = ctx.mc_paths_vr(rec, obs.astype(np.int32), int(path0), int(n_paths), steps_per_year,
+                              seed, True)
+    else:
+        out = ctx.mc_paths(rec, obs.astype(np.int32), int(path0), int(n_paths), steps_per_year,
+                           seed)
     return out[0] if single else out
 
 
-__all__ = ["monte_carlo", "simulate_paths", "MonteCarloResult", "KINDS", "MAX_OPTIONS"]
+__all__ = ["monte_carlo", "simulate_paths", "MonteCarloResult", "VarianceReducedResult", "KINDS",
+           "MAX_OPTIONS"]

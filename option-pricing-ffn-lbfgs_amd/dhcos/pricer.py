@@ -125,9 +125,12 @@ class DoubleHeston:
         return implied_vol(self.pricing(N), self.S0, self.K, self.T, self.r, self.q,
                            self.option_type, device=self.device)
 
-    def monte_carlo(self, n_paths=1 << 20, steps_per_year=64, seed=0):
+    def monte_carlo(self, n_paths=1 << 20, steps_per_year=64, seed=0, antithetic=False,
+                    control_variate=False):
         """(price, stderr) of this instance's option by simulating the model's SDE
-        (``dhcos.monte_carlo``; q must be 0, the simulated dynamics carry no dividend yield)."""
+        (``dhcos.monte_carlo``; q must be 0, the simulated dynamics carry no dividend yield).
+        antithetic, control_variate: the variance reduction of ``dhcos.monte_carlo`` (the control
+        of a European option is its discounted terminal spot)."""
         from .montecarlo import monte_carlo
         if self.q != 0.0:
             raise ValueError("monte_carlo: the simulated dynamics have q = 0")
@@ -135,7 +138,8 @@ class DoubleHeston:
                           [{"strike": self.K, "maturity": self.T,
                             "option_type": self.option_type}],
                           n_paths=n_paths, steps_per_year=steps_per_year, seed=seed,
-                          device=self.device)
+                          device=self.device, antithetic=antithetic,
+                          control_variate=control_variate)
         return np.float64(res.price[0]), np.float64(res.stderr[0])
 
     def american_monte_carlo(self, n_paths=1 << 17, steps_per_year=64, exercise_every=1, seed=0):
