@@ -164,12 +164,12 @@ struct dh_ctx {
     // the vol-space rows (dh_loss_rows.h): weight rows [B][M], each start's weight sum
     DevBuf rows_wgt, lb_div;
     // the Monte Carlo pricer (dh_mc.h): staged records, sorted options / observation steps, the
-    // blocks' partial sums, staged outputs
+    // blocks' partial sums (two per option, five under a control), staged outputs
     DevBuf mc_params, mc_opts, mc_part, mc_out;
-    // its variance reduction (dh_mc_vr.h): the blocks' five partial sums, the records with q
-    // zeroed, the twins' COS prices; the twins' surface, the (strike, maturity, type) list it was
-    // built from and the stream of the last call that read it
-    DevBuf mc_vr_part, mc_vr_rec, mc_vr_cos;
+    // its control variate (dh_mc_vr.h): the records with q zeroed, the twins' COS prices; the
+    // twins' surface, the (strike, maturity, type) list it was built from and the stream of the
+    // last call that read it
+    DevBuf mc_vr_rec, mc_vr_cos;
     dh_surface* vr_surf = nullptr;
     std::vector<double> vr_key;
     hipStream_t vr_stream = nullptr;

@@ -2766,6 +2766,6 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
 #include "dh_loss_rows.h"    // per-set market rows: dh_iv_loss.h
 #include "dh_lb_driver.h"    // the device-resident L-BFGS-B: dh_api.h, dh_iv_loss.h, dh_loss_rows.h
 #include "dh_math_probe.h"   // the device math primitives one by one: dh_host.h
-#include "dh_mc.h"           // the Monte Carlo path pricer: dh_host.h
-#include "dh_mc_vr.h"        // its antithetic pairs and control variates: dh_mc.h, dh_api.h
+#include "dh_mc.h"           // the Monte Carlo path pricer (includes dh_mc_vr.h, its control
+                             // variates): dh_host.h, dh_api.h
 #include "dh_lsm.h"          // American / Bermudan options by least-squares Monte Carlo: dh_mc.h

@@ -1,6 +1,6 @@
 // dh_lsm.h -- American and Bermudan vanilla options by the least-squares Monte Carlo method of
 // Longstaff and Schwartz (2001) on the paths of dh_mc.h (dh_lsm_price, dh_lsm_price_dev).  Included
-// by dh_kernels.hip after dh_mc.h, whose step function, constants and checks it reuses unchanged.
+// by dh_kernels.hip after dh_mc.h, whose step function, block prologue and checks it reuses.
 // DESIGN.md 3.15.1 is the contract; tests/lsm_reference.py restates the backward pass in NumPy.
 //
 // Exercise dates are the steps e, 2 e, 3 e, ... (e = exercise_every; the start value is not a
@@ -50,12 +50,8 @@ __global__ __launch_bounds__(kThreads) void lsm_paths_kernel(
     const int tid = threadIdx.x;
     const int set = blockIdx.y, slot = blockIdx.x, slots = gridDim.x;
     const double* rec = prm + (size_t)set * DH_PARAM_STRIDE;
-    if (tid == 0) {
-        dhmc::form_constants(rec, dt, sc);
-        if (slot == 0) disc[set] = exp(-rec[14] * delta);   // formed once per set
-    }
-    __syncthreads();
-    const dhmc::SetK K = dhmc::load_constants(sc);
+    if (tid == 0 && slot == 0) disc[set] = exp(-rec[14] * delta);   // formed once per set
+    const dhmc::SetK K = dhmc::block_constants(rec, dt, sc);
     double* base = state + (size_t)set * n_dates * 3 * n_paths;
     for (int64_t chunk = slot; chunk < n_chunks; chunk += slots) {
         const int64_t path = chunk * kThreads + tid;
@@ -66,7 +62,8 @@ __global__ __launch_bounds__(kThreads) void lsm_paths_kernel(
         for (int date = 0; date < n_dates; ++date) {
             for (int k = 0; k < every; ++k) {
                 ++step;
-                dhmc::mc_step(K, sc + dhmc::kCdf, dt, plo, phi, (uint32_t)step, k0, k1, s);
+                dhmc::mc_step<false>(K, sc + dhmc::kCdf, dt, plo, phi, (uint32_t)step, k0, k1, s,
+                                     s);         // no mirror: the last argument is not touched
             }
             if (active) {
                 double* o = base + (size_t)date * 3 * n_paths + path;
@@ -327,12 +324,9 @@ int check_call(const dh_lsm_option* options, int n_options, int64_t P, int64_t n
         const std::string at = " of option " + std::to_string(j);
         if (!std::isfinite(o.strike) || o.strike < 0.0)
             return fail(DH_E_ARG, "options: strike" + at + " must be finite and >= 0");
-        const double ns = o.maturity * (double)steps_per_year, n = std::rint(ns);
-        if (!std::isfinite(ns) || n < 1.0 || n > 2147483647.0 ||
-            std::fabs(ns - n) > dhmc::kStepTol * n)
-            return fail(DH_E_ARG, "options: maturity" + at + " is not a whole number (>= 1) of " +
-                                      "steps of 1 / steps_per_year");
-        const int64_t step = (int64_t)n;
+        int32_t step;
+        const int rc = dhmc::maturity_step(o.maturity, steps_per_year, at, step);
+        if (rc) return rc;
         if (step % exercise_every != 0)
             return fail(DH_E_ARG, "options: maturity" + at + " (step " + std::to_string(step) +
                                       ") is not a whole multiple of exercise_every = " +

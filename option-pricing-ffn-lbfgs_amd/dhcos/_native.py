@@ -539,6 +539,16 @@ class Context(_Handle):
                                          _addr(out, n)))
         return out
 
+    def _check_records_tensor(self, who, records):
+        """The records of a ``*_dev`` call: a contiguous float64 [P, 16] torch tensor on this
+        context's device."""
+        import torch
+        if (records.dtype != torch.float64 or not records.is_contiguous() or records.dim() != 2
+                or records.shape[1] != PARAM_STRIDE or not records.is_cuda
+                or records.device.index != self.device):
+            raise ValueError(f"{who}: a contiguous float64 [P, {PARAM_STRIDE}] tensor on "
+                             f"cuda:{self.device}")
+
     def mc_price(self, records, options, n_paths, steps_per_year, seed):
         """dh_mc_price: records [P, 16], options an array of McOption -> (price, stderr), each
         [P, n_options]."""
@@ -557,11 +567,7 @@ class Context(_Handle):
         context's own; the null stream cannot be named, as implied_vol_dev) without
         synchronisation."""
         import torch
-        if (records.dtype != torch.float64 or not records.is_contiguous() or records.dim() != 2
-                or records.shape[1] != PARAM_STRIDE or not records.is_cuda
-                or records.device.index != self.device):
-            raise ValueError(f"mc_price_dev: a contiguous float64 [P, {PARAM_STRIDE}] tensor on "
-                             f"cuda:{self.device}")
+        self._check_records_tensor("mc_price_dev", records)
         P, n_opt = records.shape[0], len(options)
         out = torch.empty((2, P, n_opt), dtype=torch.float64, device=records.device)
         st = _stream_handle("mc_price_dev", stream)
@@ -600,11 +606,7 @@ class Context(_Handle):
         device -> the six tensors of ``mc_price_vr``, enqueued on ``stream`` (None: the context's
         own; the null stream cannot be named, as mc_price_dev) without synchronisation."""
         import torch
-        if (records.dtype != torch.float64 or not records.is_contiguous() or records.dim() != 2
-                or records.shape[1] != PARAM_STRIDE or not records.is_cuda
-                or records.device.index != self.device):
-            raise ValueError(f"mc_price_vr_dev: a contiguous float64 [P, {PARAM_STRIDE}] tensor "
-                             f"on cuda:{self.device}")
+        self._check_records_tensor("mc_price_vr_dev", records)
         P, n_opt = records.shape[0], len(options)
         out = torch.empty((6, P, n_opt), dtype=torch.float64, device=records.device)
         st = _stream_handle("mc_price_vr_dev", stream)
@@ -649,11 +651,7 @@ class Context(_Handle):
         device -> the tensors of ``lsm_price``, enqueued on ``stream`` (None: the context's own;
         the null stream cannot be named, as mc_price_dev) without synchronisation."""
         import torch
-        if (records.dtype != torch.float64 or not records.is_contiguous() or records.dim() != 2
-                or records.shape[1] != PARAM_STRIDE or not records.is_cuda
-                or records.device.index != self.device):
-            raise ValueError(f"lsm_price_dev: a contiguous float64 [P, {PARAM_STRIDE}] tensor on "
-                             f"cuda:{self.device}")
+        self._check_records_tensor("lsm_price_dev", records)
         P, n_opt = records.shape[0], len(options)
         out = torch.empty((4, P, n_opt), dtype=torch.float64, device=records.device)
         coef = tau = None

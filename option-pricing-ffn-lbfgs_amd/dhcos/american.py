@@ -16,7 +16,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native
-from .montecarlo import _STEP_TOL, _check_records, _check_seed, _check_steps_per_year, _records
+from .montecarlo import (_check_records, _check_seed, _check_steps_per_year, _maturity_step,
+                         _records)
 from .pricer import resolve_call
 
 MAX_OPTIONS = _native.LSM_MAX_OPTIONS
@@ -64,15 +65,11 @@ def _options(options, steps_per_year, exercise_every):
         strike, T = float(o["strike"]), float(o["maturity"])
         if not np.isfinite(strike) or strike < 0.0:
             raise ValueError(f"options[{j}]: strike must be finite and >= 0, got {strike}")
-        ns = T * steps_per_year
-        n = np.rint(ns)
-        if not np.isfinite(ns) or n < 1 or n > 2147483647 or abs(ns - n) > _STEP_TOL * n:
-            raise ValueError(f"options[{j}]: maturity {T} is not a whole number (>= 1) of steps "
-                             f"of 1/{steps_per_year}")
-        if int(n) % exercise_every:
-            raise ValueError(f"options[{j}]: maturity {T} (step {int(n)}) is not a whole multiple "
+        n = _maturity_step(j, T, steps_per_year)
+        if n % exercise_every:
+            raise ValueError(f"options[{j}]: maturity {T} (step {n}) is not a whole multiple "
                              f"of exercise_every = {exercise_every}")
-        dates = max(dates, int(n) // exercise_every)
+        dates = max(dates, n // exercise_every)
         arr[j] = _native.LsmOption(int(resolve_call(o["option_type"])), 0, strike, T)
     return arr, dates
 

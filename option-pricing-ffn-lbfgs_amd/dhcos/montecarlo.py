@@ -131,6 +131,16 @@ def _check_seed(seed):
     return int(seed)
 
 
+def _maturity_step(j, T, steps_per_year):
+    """The step of maturity ``T`` of option ``j``: a whole number >= 1 of steps."""
+    ns = T * steps_per_year
+    n = np.rint(ns)
+    if not np.isfinite(ns) or n < 1 or n > 2147483647 or abs(ns - n) > _STEP_TOL * n:
+        raise ValueError(f"options[{j}]: maturity {T} is not a whole number (>= 1) of steps "
+                         f"of 1/{steps_per_year}")
+    return int(n)
+
+
 def _options(options, steps_per_year):
     """The reference's option dicts (strike, maturity, option_type; optional kind, barrier) ->
     an array of dh_mc_option."""
@@ -145,11 +155,7 @@ def _options(options, steps_per_year):
         strike, T = float(o["strike"]), float(o["maturity"])
         if not np.isfinite(strike) or strike < 0.0:
             raise ValueError(f"options[{j}]: strike must be finite and >= 0, got {strike}")
-        ns = T * steps_per_year
-        n = np.rint(ns)
-        if not np.isfinite(ns) or n < 1 or n > 2147483647 or abs(ns - n) > _STEP_TOL * n:
-            raise ValueError(f"options[{j}]: maturity {T} is not a whole number (>= 1) of steps "
-                             f"of 1/{steps_per_year}")
+        _maturity_step(j, T, steps_per_year)
         barrier = 0.0
         if kind in ("up_and_out", "down_and_out"):
             if "barrier" not in o:
