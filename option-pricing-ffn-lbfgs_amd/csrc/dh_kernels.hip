@@ -49,6 +49,7 @@
 #include <vector>
 
 #include "dh_device.h"
+#include "dh_index.h"
 #include "dh_lbfgs.h"
 #include "dhcos.h"
 
@@ -1615,10 +1616,12 @@ inline int tile_r(int max_nopt, int tpt) { return tpt >= 8 * std::max(max_nopt, 
 // A block-wide tile (tpt == kBlock) with kR options per group takes any G (its partials are
 // reduced through LDS, e.g. G = 10 for 100-option tiles: 250 of 256 lanes busy instead of 200 with
 // G = 8); other tiles keep a power of two <= 64 for the in-wave butterfly.
-template <int RT>
+// IDX: the index arithmetic of dh_index.h in place of `/` and `%` (the same values; the 4-wave
+// fused builds, where it pays: DESIGN 3.4).
+template <int RT, bool IDX = false>
 __device__ __forceinline__ int group_lanes(int nopt, int N, int tpt) {
     const int R = min(RT, max(nopt, 1));
-    const int ngroups = (nopt + R - 1) / R;
+    const int ngroups = IDX ? dh_idx::n_groups<RT>(nopt) : (nopt + R - 1) / R;
 #ifndef DH_GMAX
 #define DH_GMAX 1024
 #endif
@@ -1634,19 +1637,22 @@ __device__ __forceinline__ int group_lanes(int nopt, int N, int tpt) {
 // A block-wide tile (tpt == kBlock; every thread of the block must call this) whose G is not a
 // power of two <= 64 reduces each group's G lane partials through LDS (red: kR x kBlock doubles)
 // in lane order; otherwise xor butterflies inside the wave.
-template <int RT>
+template <int RT, bool IDX = false>
 __device__ __forceinline__ void tile_sums_r(const PriceArgs& A, int64_t p, const Consts& C,
                                             double S0, double disc, int nopt, int G, int tpt,
                                             int t, bool active, const TileLds& L, double* red,
                                             const double2* sct) {
     const int Ne = (int)C.ne;                     // the table's kept terms: k < n_eff
-    const int R = min(RT, max(nopt, 1));
-    const int ngroups = (nopt + R - 1) / R;
-    const int groups_per_pass = max(1, tpt / G);
+    const int R = IDX ? dh_idx::group_r<RT>(nopt) : min(RT, max(nopt, 1));
+    const int ngroups = IDX ? dh_idx::n_groups<RT>(nopt) : (nopt + R - 1) / R;
+    // IDX: t / G and t % G as a 24-bit multiply by gm and a shift (t < tpt <= 256, G <= 256)
+    const unsigned gm = IDX ? dh_idx::div256_magic(G) : 0u;
+    const int groups_per_pass = max(1, IDX ? (int)dh_idx::div256(tpt, gm) : tpt / G);
     const bool lds_red = tpt == kBlock && (G > 64 || (G & (G - 1)) != 0);   // else butterflies
     for (int pass = 0; pass < ngroups; pass += groups_per_pass) {
-        const int gi = pass + t / G;
-        const int gl = t % G;
+        const int tg = IDX ? (int)dh_idx::div256(t, gm) : t / G;
+        const int gi = pass + tg;
+        const int gl = IDX ? (int)dh_idx::mod256(t, tg, G) : t % G;
         const bool gvalid = active && t < groups_per_pass * G && gi < ngroups;
         double dx[RT], cs[RT], ss[RT];
         bool use[RT];
@@ -1682,8 +1688,9 @@ __device__ __forceinline__ void tile_sums_r(const PriceArgs& A, int64_t p, const
             const int o_end = min(nopt, min(pass + groups_per_pass, ngroups) * R);
             for (int oi = pass * R + t; active && oi < o_end; oi += tpt) {
                 if (!isnan(L.ss[oi])) {
-                    const int j = oi % R;
-                    const double* rj = red + j * kBlock + (oi / R - pass) * G;
+                    const int j = IDX ? dh_idx::opt_slot<RT>(oi, nopt) : oi % R;
+                    const int og = IDX ? dh_idx::opt_group<RT>(oi, nopt) : oi / R;
+                    const double* rj = red + j * kBlock + (og - pass) * G;
                     double sum = 0.0;
                     for (int l = 0; l < G; ++l) sum += rj[l];
                     const double v = option_sum(C, L.call[oi] != 0, S0, L.K[oi], L.xK[oi],
@@ -2321,9 +2328,16 @@ __global__ __launch_bounds__(kBlock, WV) void cos_fused_kernel(
     const int lane = t & 63;
     const int wv = t >> 6;
     const int64_t q = blockIdx.x;                       // dispatch index
-    const int64_t qt = xcd_table(A, H.tpp, q);          // the table it prices
-    const int64_t p = (int64_t)((unsigned)qt / (unsigned)H.tpp);   // 32-bit: grids < 2^31 blocks
-    const int g = (int)((unsigned)qt % (unsigned)H.tpp);
+    // index arithmetic without per-lane divisions (dh_index.h) in the 4-wave builds; the 5-wave
+    // build keeps `/` and `%`: with them replaced its register allocation cost C4 2%
+    constexpr bool kIdx = WV <= DH_FUSED_WAVES;
+    // the table it prices (block-uniform: said so, its decomposition runs on the scalar unit)
+    const int64_t qt = kIdx ? (int64_t)(unsigned)__builtin_amdgcn_readfirstlane(
+                                  (int)xcd_table(A, H.tpp, q))
+                            : xcd_table(A, H.tpp, q);
+    int64_t p;                                          // 32-bit: grids < 2^31 blocks
+    int g;
+    dh_idx::table_split(qt, H.tpp, p, g);
     DH_RT_BEGIN(A);
     DH_STAMP(A, 0);
 
@@ -2381,7 +2395,7 @@ __global__ __launch_bounds__(kBlock, WV) void cos_fused_kernel(
     const double S0 = prm[13];
     dh::load_math_tables(sct, nthr > 64 ? 64 : 0);      // the waves after the prologue's
     // staging order: waves 1, 2, .., then 0 (its prologue first)
-    for (int i = (t + nthr - 64) % nthr; i < gn; i += nthr) {
+    for (int i = kIdx ? dh_idx::rot64(t, nthr) : (t + nthr - 64) % nthr; i < gn; i += nthr) {
         const int m = g0 + i;
         const double K = option_strike(A, m, S0);
         double ratio;
@@ -2529,10 +2543,11 @@ __global__ __launch_bounds__(kBlock, WV) void cos_fused_kernel(
         }
     }
     const double disc = shc[29];                    // e^{-rT}, staged by the prologue
-    const int G = group_lanes<RT>(gn, N, tpt2);
+    const int G = group_lanes<RT, kIdx>(gn, N, tpt2);
     {
         const double ustep = G * dh::kPi / (b - a);
-        for (int i = (t + nthr - 64) % nthr; i < gn; i += nthr) {          // wave 0 does the sums
+        // (wave 0 does the sums)
+        for (int i = kIdx ? dh_idx::rot64(t, nthr) : (t + nthr - 64) % nthr; i < gn; i += nthr) {
             const bool cl = (cmask[i >> 6] >> (i & 63)) & 1ull;
             double ss, cs;
             dh::dsincos(ustep * (cl ? 0.0 : L.xK[i] - a), &ss, &cs);
@@ -2546,7 +2561,8 @@ __global__ __launch_bounds__(kBlock, WV) void cos_fused_kernel(
     DH_STAMP(A, 3);
 
     const Consts C{0.0 + red[0][0], 0.0 + red[1][0], 0.0 + red[2][0], 0.0 + red[3][0], a, b, eb, ea};
-    if (t < tpt2) tile_sums_r<RT>(A, p, C, S0, disc, gn, G, tpt2, t, true, L, lclp + cap, sct);
+    if (t < tpt2)
+        tile_sums_r<RT, kIdx>(A, p, C, S0, disc, gn, G, tpt2, t, true, L, lclp + cap, sct);
     DH_STAMP(A, 4);
     // (a block-wide tile reduced through LDS has just passed tile_sums' closing barrier, after
     // its last loss terms were written, so a second one is not needed; measured, dropping it was
