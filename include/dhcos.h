@@ -102,6 +102,14 @@ int dh_surface_create(dh_ctx* ctx, const double* K, const double* T, const int8_
                       const double* mkt, int M, int strike_mode, dh_surface** out);
 int dh_surface_destroy(dh_surface* s);
 int dh_surface_size(const dh_surface* s, int* M, int* n_tiles);
+/* Form, once, what the request kernels otherwise form per table from the spot and the surface
+ * alone: log(K / S0) and K / S0 of every option (DH_STRIKE_PCT_SPOT: the strike K_relative * S0 /
+ * 100.0 too), by the kernels' own device functions, so the same bits.  A fused request block whose
+ * record carries exactly this S0 (the same 64 bits) loads the values; any other record, and every
+ * request on a surface never staged, computes them as before.  S0 finite and > 0; calling it again
+ * restages.  Runs on the context's stream and waits for it: requests on any stream may follow.
+ * Not to be called while a request on the surface is in flight.                                 */
+int dh_surface_stage_spot(dh_surface* s, double S0);
 
 /* Price every option of the surface under every param set: out[p*M + m], m in the caller's
  * original option order.  Replaces DoubleHeston.pricing(N) (double_heston.py:160-192) called

@@ -221,7 +221,39 @@ int dh_surface_destroy(dh_surface* s) {
     DeviceScope dev_scope(s->ctx ? s->ctx->device : 0);
     if (s->block) (void)hipFree(s->block);
     if (s->iv_block) (void)hipFree(s->iv_block);
+    if (s->spot_block) (void)hipFree(s->spot_block);
     delete s;
+    return DH_OK;
+}
+
+int dh_surface_stage_spot(dh_surface* s, double S0) {
+    if (!s || !s->ctx) return fail(DH_E_ARG, "surface is null");
+    if (!(S0 > 0.0) || std::isinf(S0)) return fail(DH_E_ARG, "S0 must be finite and > 0");
+    if (s->M == 0) return DH_OK;
+    dh_ctx* ctx = s->ctx;
+    DeviceScope dev_scope(ctx->device);
+    if (dev_scope.rc) return dev_scope.rc;
+    const size_t m = (size_t)s->M;
+    if (!s->spot_block) {
+        HIP_TRY(hipMalloc(&s->spot_block, 3 * m * sizeof(double)));
+    }
+    double* base = (double*)s->spot_block;
+    // off while the arrays are rewritten, and for good should the launch fail
+    s->spot_staged = kSpotNone;
+    s->xk_s = s->exk_s = s->k_s = nullptr;
+    PriceArgs A{};
+    A.K = s->K;
+    A.strike_mode = s->strike_mode;
+    A.M = s->M;
+    hipLaunchKernelGGL(stage_spot_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock),
+                       0, ctx->stream, A, S0, base + 2 * m, base, base + m);
+    HIP_TRY(hipGetLastError());
+    // once per surface: requests on any stream (the SciPy loop's slots) then need no ordering
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    s->xk_s = base;
+    s->exk_s = base + m;
+    s->k_s = base + 2 * m;
+    std::memcpy(&s->spot_staged, &S0, sizeof(S0));
     return DH_OK;
 }
 
@@ -257,6 +289,10 @@ static PriceArgs surface_args(const dh_ctx* ctx, const dh_surface* s, const doub
     A.N = N;
     A.L = L;
     A.out_stride = s->M;
+    A.xk_s = s->xk_s;                      // null until dh_surface_stage_spot
+    A.exk_s = s->exk_s;
+    A.k_s = s->k_s;
+    A.spot_staged = s->spot_staged;
     return A;
 }
 

@@ -179,6 +179,9 @@ struct dh_ctx {
     DevBuf lsm_state, lsm_cash, lsm_tau, lsm_part, lsm_fin, lsm_opts, lsm_disc, lsm_coef, lsm_out;
 };
 
+// dh_surface::spot_staged before any staging: a NaN's bits, which dh_surface_stage_spot refuses
+constexpr uint64_t kSpotNone = ~uint64_t(0);
+
 struct dh_surface {
     dh_ctx* ctx = nullptr;
     int M = 0;
@@ -204,7 +207,15 @@ struct dh_surface {
     double* iv_mkt = nullptr;
     double* iv_wgt = nullptr;
     void* iv_block = nullptr;
-    std::vector<double> h_group_T;   // host copies of group_T / groups (the fused launch's
+    // dh_surface_stage_spot (dh_api.h): log(K / S0), K / S0 and the strike (K itself unless
+    // DH_STRIKE_PCT_SPOT) [M] in the sorted option order, formed for the S0 whose 64 bits
+    // spot_staged holds, in an allocation of their own
+    uint64_t spot_staged = kSpotNone;
+    double* xk_s = nullptr;
+    double* exk_s = nullptr;
+    double* k_s = nullptr;
+    void* spot_block = nullptr;
+    std::vector<double> h_group_T;  // host copies of group_T / groups (the fused launch's
     std::vector<int2> h_groups;      // kernel arguments, KargParams)
 };
 

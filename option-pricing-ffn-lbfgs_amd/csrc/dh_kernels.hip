@@ -135,6 +135,13 @@ struct PriceArgs {
     int remap;              // fused kernel: dispatch index -> table by XCD (xcd_table), else 0
     int host_out;           // sse / n_bad in mapped host memory (the host API's zero-copy
                             // requests): written by system-scope stores, drained (loss_out)
+    // the surface's spot cache (dh_surface_stage_spot; xk_s null: off): [M] log(K / S0), K / S0
+    // and the strike option_strike gives, formed for the S0 whose bits are spot_staged.  The
+    // fused kernel's blocks whose record carries those bits load them instead of computing them
+    const double* xk_s;
+    const double* exk_s;
+    const double* k_s;
+    unsigned long long spot_staged;
 };
 
 // w_k of table q sits at table_w(A, q)[k * table_step(A)].  The small-tile option kernel has one
@@ -206,6 +213,23 @@ __device__ __forceinline__ double option_logk(double K, double S0, double& ratio
 __device__ __forceinline__ double option_strike(const PriceArgs& A, int m, double S0) {
     const double Kin = A.K[m];
     return (A.strike_mode == DH_STRIKE_PCT_SPOT) ? Kin * S0 / 100.0 : Kin;
+}
+
+// dh_surface_stage_spot: the two functions above for every option of the surface under one spot,
+// once (A: K, strike_mode and M).  The fused kernel's staging loop forms the same values by the
+// same functions, so a block may load these instead.
+__global__ __launch_bounds__(kBlock) void stage_spot_kernel(PriceArgs A, double S0,
+                                                            double* __restrict__ k_s,
+                                                            double* __restrict__ xk_s,
+                                                            double* __restrict__ exk_s) {
+    const int m = blockIdx.x * kBlock + threadIdx.x;
+    if (m >= A.M) return;
+    const double K = option_strike(A, m, S0);
+    double ratio;
+    const double xK = option_logk(K, S0, ratio);
+    k_s[m] = K;
+    xk_s[m] = xK;
+    exk_s[m] = ratio;
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -549,8 +573,8 @@ static_assert(sizeof(FusedKargs) + 256 >= 0x1b4, "kernel-argument prefetch past 
 // launch's kernel-argument segment, which the runtime writes to device memory ahead of the
 // dispatch, instead of being read by the blocks from mapped host memory across PCIe at the start
 // of the request's critical path (C1: 11.9 -> 10.1 us per kernel with the records in HBM).  One
-// start's 14 records: 1,792 bytes, 2,416 with the rest of the arguments and 2,672 with the
-// runtime's hidden ones (28 records would pass the 4 KiB segment).
+// start's 14 records: 1,792 bytes, 2,720 with the rest of the arguments (the groups below among
+// them) and 2,976 with the runtime's hidden ones (28 records would pass the 4 KiB segment).
 constexpr int kKargSets = 14;
 // and, for surfaces of at most kKargGroups maturity groups (C1's 3, C2's 32), the groups' maturities
 // and option ranges: the prologue's first dependent load (the table's T) then comes from the
@@ -569,7 +593,7 @@ struct FusedKargsKP {       // cos_fused_kernel<..., true>'s argument list
     int tpt2;
     KargParams pb;
 };
-constexpr int kFusedParamsKernargOff = 384;
+constexpr int kFusedParamsKernargOff = 416;
 static_assert(offsetof(FusedKargsKP, pb) == kFusedParamsKernargOff, "param block kernarg offset");
 static_assert(sizeof(FusedKargsKP) + 256 <= 4096, "kernel arguments over 4 KiB");
 
@@ -2394,12 +2418,30 @@ __global__ __launch_bounds__(kBlock, WV) void cos_fused_kernel(
     const double* prm = H.prm + p * DH_PARAM_STRIDE;
     const double S0 = prm[13];
     dh::load_math_tables(sct, nthr > 64 ? 64 : 0);      // the waves after the prologue's
+    // the surface's spot cache (dh_surface_stage_spot) holds this record's spot, bit for bit: the
+    // strike, its log-moneyness and K / S0 are loaded, not formed (an fp64 division and a log per
+    // option and table less).  Block-uniform, decided on the scalar unit; the 4-wave builds only
+    // (the 5-wave build's register allocation is left alone, as with kIdx).  Whether the surface
+    // has a cache is known from the kernel arguments alone, so its loads issue beside the
+    // record's (S0) and not behind it; the compare then keeps them or forms the values
+    // (measured with the loads inside the branch on the compare: C2 +0.09 us)
+    constexpr bool kSpot = WV <= DH_FUSED_WAVES;
+    const bool cached = kSpot && A.xk_s != nullptr;
     // staging order: waves 1, 2, .., then 0 (its prologue first)
     for (int i = kIdx ? dh_idx::rot64(t, nthr) : (t + nthr - 64) % nthr; i < gn; i += nthr) {
         const int m = g0 + i;
-        const double K = option_strike(A, m, S0);
-        double ratio;
-        const double xK = option_logk(K, S0, ratio);
+        double K = 0.0, xK = 0.0, ratio = 0.0;
+        if (cached) {
+            K = A.k_s[m];
+            xK = A.xk_s[m];
+            ratio = A.exk_s[m];
+        }
+        const bool staged = cached && __builtin_amdgcn_readfirstlane((int)(
+            (unsigned long long)__double_as_longlong(S0) == A.spot_staged));
+        if (!staged) {
+            K = option_strike(A, m, S0);
+            xK = option_logk(K, S0, ratio);
+        }
         L.K[i] = K;
         L.mkt[i] = A.mkt ? A.mkt[m] : 0.0;
         L.call[i] = A.call[m];

@@ -101,6 +101,7 @@ SIGNATURES = {
     "dh_surface_create": (_int, [_vp, _dp, _dp, _i8p, _dp, _int, _int, C.POINTER(_vp)]),
     "dh_surface_destroy": (_int, [_vp]),
     "dh_surface_size": (_int, [_vp, _i32p, _i32p]),
+    "dh_surface_stage_spot": (_int, [_vp, _dbl]),
     "dh_surface_price": (_int, [_vp, _vp, _dp, _i64, _int, _dbl, _dp]),
     "dh_surface_price_cols": (_int, [_vp, _vp, _dp, _dp, _dbl, _i64, _int, _dbl, _dp]),
     "dh_host_register": (_int, [_vp, C.c_size_t]),
@@ -814,6 +815,12 @@ class Surface(_Handle):
         if self._h:
             load().dh_surface_destroy(self._h)
             self._h = None
+
+    def stage_spot(self, S0):
+        """dh_surface_stage_spot: form log(K / S0) and K / S0 of every option once; fused request
+        blocks whose record carries exactly this spot then load them (the same bits)."""
+        with self.ctx._lock:
+            _check(load().dh_surface_stage_spot(self._h, float(S0)))
 
     def _market_rows(self, mkt):
         """Market rows (prices or vols) as a contiguous float64 [B, M]."""

@@ -291,12 +291,16 @@ class DoubleHestonJumpCalibrator:
             ctx = _native.default_context(self.device)
             K, T = self._option_arrays()
             surf = _native.Surface(ctx, K, T, flags, self.market_prices)
-            if self.objective == "iv":
-                try:
+            try:
+                # one spot for the whole run: log(K / S0) and K / S0 once, not once per table
+                # (a spot the library would refuse leaves the surface unstaged: the same prices)
+                if isinstance(self.spot, (float, int)) and 0 < self.spot < np.inf:
+                    surf.stage_spot(self.spot)
+                if self.objective == "iv":
                     self._set_iv_market(surf, K, T, flags)
-                except BaseException:
-                    surf.close()
-                    raise
+            except BaseException:
+                surf.close()
+                raise
             self._surface = surf
             self._surface_ok = True
         return self._surface if self._surface_ok else None
