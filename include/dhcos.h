@@ -356,6 +356,44 @@ int dh_host_cache_trim(void);
 int dh_price_pairs(dh_ctx* ctx, const double* params, const double* K, const double* T,
                    const int8_t* is_call, int64_t P, int N, double L, double* out);
 
+/* ---- analytic Greeks of the COS price (csrc/dh_greeks.h) --------------------- */
+/* Replaces nothing in the reference (it has no sensitivities): it replaces bumping and repricing,
+ * nine pricings for the five sensitivities below by central differences.  With xK = log(K / S0),
+ * [a, b] = truncationRange(L), u_k = k pi / (b - a), w_k = phi(u_k) e^{-i u_k a}, the price is
+ *     e^{-rT} sum'_{k < N} Re(w_k) V_k,  V_k = +-(2 / (b - a)) (S0 chi_k - K psi_k)
+ * (double_heston.py:160-192; chi_k, psi_k over [xK, b] and + for a call, over [a, xK] and - for a
+ * put), and the planes are the partial derivatives of this series at FIXED [a, b] and fixed
+ * absolute strike (a DH_STRIKE_PCT_SPOT strike is first resolved to K_relative * S0 / 100.0):
+ *     DH_GREEK_PRICE       the series itself
+ *     DH_GREEK_DELTA       d / dS0:     V_k -> +-(2 / (b - a)) chi_k
+ *     DH_GREEK_GAMMA       d2 / dS0^2:  V_k -> (2 / (b - a)) cos(u_k (xK - a)) K / S0^2
+ *     DH_GREEK_DUAL_DELTA  d / dK:      V_k -> -+(2 / (b - a)) psi_k
+ *     DH_GREEK_VEGA1       d / dv01:    w_k -> w_k B1(u_k)   (B_j: the CF's variance-factor
+ *     DH_GREEK_VEGA2       d / dv02:    w_k -> w_k B2(u_k)    coefficients; per unit of variance)
+ * They do NOT differentiate through the cumulant range or through the log(K / S0) -+ 0.1 clamp
+ * (double_heston.py:131-137): the difference from a total derivative is of the size of the series'
+ * truncation error where the clamp is inactive and is not small where it is active.
+ * price = S0 delta + K dual_delta holds to rounding.  Every term k < N is summed (the price path's
+ * adaptive tail cut is not applied: gamma's coefficients do not decay), every sum in a fixed order:
+ * the same call gives the same bits, and an option's values do not depend on what shares its call.
+ * q is supported as for prices.  Non-finite parameters give NaN in every plane, as prices do.
+ * DH_E_ARG, before any device work and naming the argument in dh_last_error(): N outside
+ * [1, DH_MAX_N]; P (n) < 1; L not finite or <= 0; a NULL pointer.                               */
+enum { DH_GREEK_PRICE, DH_GREEK_DELTA, DH_GREEK_GAMMA, DH_GREEK_DUAL_DELTA, DH_GREEK_VEGA1,
+       DH_GREEK_VEGA2, DH_N_GREEKS };
+/* out[(g * P + p) * M + m], g a DH_GREEK_* plane, m in the caller's option order as in
+ * dh_surface_price.  Host arrays, synchronous.                                                  */
+int dh_surface_greeks(dh_ctx* ctx, const dh_surface* s, const double* params, int64_t P, int N,
+                      double L, double* out);
+/* The same over device pointers: enqueued on `stream` (hipStream_t; NULL = the context's) without
+ * synchronisation, no allocation; the same bits as dh_surface_greeks.                           */
+int dh_surface_greeks_dev(dh_ctx* ctx, const dh_surface* s, const double* d_params, int64_t P,
+                          int N, double L, double* d_out, void* stream);
+/* Option i under param set i, the counterpart of dh_price_pairs: out[g * n + i].  Host arrays,
+ * synchronous; the bits dh_surface_greeks gives the same (set, option) pair.                    */
+int dh_greeks_pairs(dh_ctx* ctx, const double* params, const double* K, const double* T,
+                    const int8_t* is_call, int64_t n, int N, double L, double* out);
+
 /* ---- Black-Scholes implied volatility ----------------------------------------------------- */
 /* sigma[i] = the volatility whose Black-Scholes price of (S0[i], K[i], T[i], r[i], q[i],
  * is_call[i]) is price[i]; every array has n entries (structure of arrays), one GPU lane per quote.

@@ -573,7 +573,8 @@ __device__ __forceinline__ FactorC factor_consts(double v0, double kap, double t
 
 // One factor's contribution X to the exponent E: kappa theta / sigma^2 ((beta - d) tau - 2 log Q)
 // + B v0.  E = ((D + X1) + X2) + J with D = (0, drift u) and J the jump part, in that order in every
-// path, so every path agrees.
+// path, so every path agrees.  (dh_greeks.h's factor_x_b is this function with B handed out for the
+// vegas: a change here belongs there too.)
 __device__ __forceinline__ cplx factor_x(const FactorC& F, double u, double tau,
                                          const double2* __restrict__ sct) {
     const cplx beta = {F.kap, -(F.rs * u)};

@@ -176,7 +176,9 @@ struct dh_ctx {
     // the least-squares Monte Carlo pricer (dh_lsm.h): the states at the exercise dates, each
     // option's cashflow and exercise date per path, the blocks' normal-equation and price
     // partials, options, per-set discounts, coefficients, staged outputs
-    DevBuf lsm_state, lsm_cash, lsm_tau, lsm_part, lsm_fin, lsm_opts, lsm_disc, lsm_coef, lsm_out;
+    DevBuf lsm_state, lsm_cash, lsm_tau, lsm_part, lsm_fin, lsm_opts, lsm_disc, lsm_coef, lsm_out;    // the Greeks kernel (dh_greeks.h): the dynamic-LDS cap raised for it on this context's device
+    // (bytes; 0: not yet)
+    int greeks_lds = 0;
 };
 
 // dh_surface::spot_staged before any staging: a NaN's bits, which dh_surface_stage_spot refuses

@@ -2827,3 +2827,4 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
 #include "dh_mc.h"           // the Monte Carlo path pricer (includes dh_mc_vr.h, its control
                              // variates): dh_host.h, dh_api.h
 #include "dh_lsm.h"          // American / Bermudan options by least-squares Monte Carlo: dh_mc.h
+#include "dh_greeks.h"       // analytic Greeks of the COS price: dh_host.h

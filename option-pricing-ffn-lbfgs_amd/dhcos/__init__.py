@@ -11,6 +11,8 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
     monte_carlo                       (new: path pricing of European, Asian and barrier options,
                                        with antithetic pairs and COS-priced control variates)
     american_monte_carlo              (new: American and Bermudan options by least-squares Monte Carlo)
+    greeks                            (new: analytic delta, gamma, dual delta and v0 vegas of the
+                                       COS price, one pass; the module itself is dhcos/greeks.py)
 
 All pricing arithmetic runs in libdhcos.so (hand-written gfx950 HIP kernels, C-ABI in
 include/dhcos.h); the native library is loaded on first use and there is no CPU fallback.
@@ -24,11 +26,12 @@ from .generator import generate_synthetic_calibrations
 from .batch import BatchCalibrationResult, calibrate_batch
 from .montecarlo import MonteCarloResult, VarianceReducedResult, monte_carlo
 from .american import AmericanMonteCarloResult, american_monte_carlo
+from .greeks import Greeks, greeks
 from ._native import NativeError
 
 __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
            "generate_synthetic_calibrations", "implied_vol", "NativeError", "calibrate_batch",
            "BatchCalibrationResult", "monte_carlo", "MonteCarloResult",
            "VarianceReducedResult",
-           "american_monte_carlo", "AmericanMonteCarloResult"]
+           "american_monte_carlo", "AmericanMonteCarloResult", "greeks", "Greeks"]
 __version__ = "0.1.0"

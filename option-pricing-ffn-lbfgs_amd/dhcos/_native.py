@@ -42,6 +42,8 @@ LSM_MIN_ITM = 64               # DH_LSM_MIN_ITM: in-the-money paths a date needs
 LSM_SLOTS = 128                # DH_LSM_SLOTS: blocks per (set, option) of a backward launch
 LSM_MAX_GIB = 16               # DH_LSM_MAX_GIB: cap of the path store
 STAMPS_PER_BLOCK = 32          # kStamps of the DH_STAMPS build (csrc/dh_kernels.hip)
+# the planes of dh_surface_greeks / dh_greeks_pairs, in the order of the header's DH_GREEK_* enum
+GREEKS = ("price", "delta", "gamma", "dual_delta", "vega1", "vega2")
 
 _dp = C.POINTER(C.c_double)
 _i8p = C.POINTER(C.c_int8)
@@ -147,6 +149,10 @@ SIGNATURES = {
     "dh_host_cache_trim": (_int, []),
     # ---- paired pricing
     "dh_price_pairs": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _dbl, _vp]),
+    # ---- analytic Greeks of the COS price
+    "dh_surface_greeks": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp]),
+    "dh_surface_greeks_dev": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp, _vp]),
+    "dh_greeks_pairs": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _dbl, _vp]),
     # ---- Black-Scholes implied volatility
     "dh_implied_vol": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dh_implied_vol_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
@@ -483,6 +489,18 @@ class Context(_Handle):
         with self._lock:
             _check(load().dh_price_pairs(self._h, params.ctypes.data, K.ctypes.data, T.ctypes.data,
                                          ic.ctypes.data, P, int(N), float(L), out.ctypes.data))
+        return out
+
+    def greeks_pairs(self, params, K, T, is_call, N=128, L=10.0):
+        """dh_greeks_pairs: the planes GREEKS of option i under param record i -> [6, n]."""
+        params = _records(params)
+        n = params.shape[0]
+        K, T = _f64(K).reshape(n), _f64(T).reshape(n)
+        ic = _flags(is_call, n)
+        out = np.empty((len(GREEKS), n))
+        with self._lock:
+            _check(load().dh_greeks_pairs(self._h, _addr(params, n), _addr(K, n), _addr(T, n),
+                                          _addr(ic, n), n, int(N), float(L), _addr(out, n)))
         return out
 
     def price_batch(self, params, K, T, is_call, N=128, L=10.0):
@@ -1040,7 +1058,24 @@ class Surface(_Handle):
                                              _addr(prices), _addr(iv)))
         return ret
 
+    def greeks(self, params, N=128, L=10.0):
+        """dh_surface_greeks: the planes GREEKS (price, delta, gamma, dual delta, the two v0
+        vegas) of every option under every param row -> [6, P, M].  Partial derivatives of the
+        COS series at a fixed truncation range and strike (include/dhcos.h)."""
+        params = _records(params)
+        P = params.shape[0]
+        out = np.empty((len(GREEKS), P, self.M))
+        with self.ctx._lock:
+            _check(load().dh_surface_greeks(self.ctx.handle, self._h, _addr(params, P), P, int(N),
+                                            float(L), out.ctypes.data))
+        return out
+
     # device-pointer variants (torch tensors or raw device addresses)
+    def greeks_dev(self, d_params: int, P: int, d_out: int, N=128, L=10.0, stream: int = 0):
+        """dh_surface_greeks_dev: d_params [P, 16] in, d_out [6, P, M] out, enqueued on stream."""
+        _check(load().dh_surface_greeks_dev(self.ctx.handle, self._h, _addr(d_params), int(P),
+                                            int(N), float(L), _addr(d_out), _addr(stream)))
+
     def price_dev(self, d_params: int, P: int, d_out: int, N=128, L=10.0, stream: int = 0):
         _check(load().dh_surface_price_dev(self.ctx.handle, self._h, d_params, int(P), int(N),
                                            float(L), d_out, _addr(stream)))
@@ -1567,7 +1602,7 @@ __all__ = [
     "LIB_PATH", "SIGNATURES", "NativeError", "load", "runtime_shared_with_torch", "device_count",
     "resolve_device", "default_context", "PARAM_STRIDE", "MAX_N", "MAX_N_PER_TERM",
     "STRIKE_ABSOLUTE", "STRIKE_PCT_SPOT", "PATH_AUTO", "PATH_SPLIT", "PATH_FUSED", "PATH_GEN",
-    "FG_SLOTS", "STAMPS_PER_BLOCK",
+    "FG_SLOTS", "STAMPS_PER_BLOCK", "GREEKS",
     "Context", "Surface", "FgChannel", "pinned", "pinned_empty", "host_cache_trim",
     "LbOptions", "LbResult", "lb_batch_args", "iv_rows",
     "gen_draw", "GenDraw", "GEN_LOC_WORDS", "gen_locate", "gen_draw_located", "gen_sweep",

@@ -47,6 +47,27 @@ def _is_call_array(option_type) -> np.ndarray:
     return ot.astype(bool)
 
 
+def _pair_args(params, S0, K, T, r, option_type, q):
+    """price_batch's arguments as (records [n, 16], K [n], T [n], is_call [n]) of n pairs."""
+    params = np.atleast_2d(np.asarray(params, dtype=np.float64))
+    n = max(params.shape[0], np.size(K), np.size(T), np.size(S0))
+    P = np.broadcast_to(params, (n, 13))
+    rec = np.empty((n, _native.PARAM_STRIDE))
+    rec[:, :13] = P
+    rec[:, 13] = np.broadcast_to(np.asarray(S0, dtype=np.float64), (n,))
+    rec[:, 14] = np.broadcast_to(np.asarray(r, dtype=np.float64), (n,))
+    rec[:, 15] = np.broadcast_to(np.asarray(q, dtype=np.float64), (n,))
+    if isinstance(option_type, str):
+        ic = np.full(n, resolve_call(option_type))
+    else:
+        ot = list(option_type)
+        ic = np.array([resolve_call(o) if isinstance(o, str) else bool(o) for o in ot])
+        ic = np.broadcast_to(ic, (n,))
+    Kb = np.broadcast_to(np.asarray(K, dtype=np.float64), (n,))
+    Tb = np.broadcast_to(np.asarray(T, dtype=np.float64), (n,))
+    return rec, Kb, Tb, ic
+
+
 def implied_vol(price, S0, K, T, r, q=0.0, option_type="C", device=None):
     """Black-Scholes implied volatility on the GPU (dh_implied_vol): the sigma whose price of a
     European option (spot S0, strike K, maturity T, rate r, dividend yield q) is ``price``.
@@ -125,6 +146,16 @@ class DoubleHeston:
         return implied_vol(self.pricing(N), self.S0, self.K, self.T, self.r, self.q,
                            self.option_type, device=self.device)
 
+    def greeks(self, N=128):
+        """``Greeks`` (price, delta, gamma, dual_delta, vega1, vega2) of this instance's option as
+        scalars: the analytic partial derivatives of ``pricing(N)``'s COS series at a fixed
+        truncation range and strike -- not through the cumulant range or its log-strike clamp
+        (``dhcos.greeks``; the vegas are per unit of the variances v01, v02)."""
+        from .greeks import Greeks, check_N
+        out = self._ctx().greeks_pairs(self._record(), [float(self.K)], [float(self.T)],
+                                       [resolve_call(self.option_type)], check_N(N))
+        return Greeks.from_planes(out[:, 0])
+
     def monte_carlo(self, n_paths=1 << 20, steps_per_year=64, seed=0, antithetic=False,
                     control_variate=False):
         """(price, stderr) of this instance's option by simulating the model's SDE
@@ -164,23 +195,19 @@ class DoubleHeston:
         params: [n, 13] model parameters (constructor order); S0, K, T, r, q broadcast to n;
         option_type: a string or a sequence of n strings (reference rule) or booleans (is_call).
         """
-        params = np.atleast_2d(np.asarray(params, dtype=np.float64))
-        n = max(params.shape[0], np.size(K), np.size(T), np.size(S0))
-        P = np.broadcast_to(params, (n, 13))
-        rec = np.empty((n, _native.PARAM_STRIDE))
-        rec[:, :13] = P
-        rec[:, 13] = np.broadcast_to(np.asarray(S0, dtype=np.float64), (n,))
-        rec[:, 14] = np.broadcast_to(np.asarray(r, dtype=np.float64), (n,))
-        rec[:, 15] = np.broadcast_to(np.asarray(q, dtype=np.float64), (n,))
-        if isinstance(option_type, str):
-            ic = np.full(n, resolve_call(option_type))
-        else:
-            ot = list(option_type)
-            ic = np.array([resolve_call(o) if isinstance(o, str) else bool(o) for o in ot])
-            ic = np.broadcast_to(ic, (n,))
-        Kb = np.broadcast_to(np.asarray(K, dtype=np.float64), (n,))
-        Tb = np.broadcast_to(np.asarray(T, dtype=np.float64), (n,))
+        rec, Kb, Tb, ic = _pair_args(params, S0, K, T, r, option_type, q)
         return _native.default_context(device).price_pairs(rec, Kb, Tb, ic, N, L)
+
+    @staticmethod
+    def greeks_batch(params, S0, K, T, r, option_type="C", N=128, q=0.0, L=10.0, device=None):
+        """``price_batch``'s arguments -> ``Greeks`` of ``[n]`` arrays: price, delta, gamma,
+        dual_delta, vega1, vega2 of option i under param set i, all in one launch.  Partial
+        derivatives of the COS series at a fixed truncation range and strike (``dhcos.greeks``)."""
+        from .greeks import Greeks, check_L, check_N
+        N, L = check_N(N), check_L(L)
+        rec, Kb, Tb, ic = _pair_args(params, S0, K, T, r, option_type, q)
+        return Greeks.from_planes(
+            _native.default_context(device).greeks_pairs(rec, Kb, Tb, ic, N, L))
 
     @staticmethod
     def implied_vol_batch(params, S0, K, T, r, option_type="C", N=128, q=0.0, L=10.0,
