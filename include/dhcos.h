@@ -394,6 +394,64 @@ int dh_surface_greeks_dev(dh_ctx* ctx, const dh_surface* s, const double* d_para
 int dh_greeks_pairs(dh_ctx* ctx, const double* params, const double* K, const double* T,
                     const int8_t* is_call, int64_t n, int N, double L, double* out);
 
+/* ---- analytic parameter sensitivities and the calibration gradient (csrc/dh_param_grad.h,
+ * DESIGN.md 3.18) --------------------------------------------------------------------------- */
+/* Replaces nothing in the reference (it has no sensitivities and hands SciPy no gradient): it
+ * replaces bumping and repricing, the fourteen pricings of a forward-difference request
+ * (dh_surface_fg).  In the Greeks' notation, for a model parameter p at FIXED [a, b]
+ *     d price / d p = e^{-rT} sum'_{k < N} Re(w_k D_p(u_k)) V_k,   D_p = d log phi / d p
+ * (the closed forms of the thirteen D_p: csrc/dh_param_grad.h).  Like the Greeks the planes do NOT
+ * differentiate through the cumulant range or its log(K / S0) -+ 0.1 clamp.  Plane 0 is the price,
+ * planes 1..13 the parameters in the record's order: v1_0 kappa1 theta1 sigma1 rho1 v2_0 kappa2
+ * theta2 sigma2 rho2 lambda_j mu_j sigma_j.  Planes 0, 1 and 6 are the same series as
+ * dh_surface_greeks' price and vegas and agree with them to rounding (1e-13 at S0 = 100), not bit
+ * for bit.  Every term k < N is summed in a fixed order: the same call
+ * gives the same bits, and a set's values do not depend on what shares its call.  Non-finite
+ * parameters give NaN in every plane.
+ * DH_E_ARG, before any device work and naming the argument in dh_last_error(): N outside
+ * [1, DH_PARAM_GRAD_MAX_N] (sixteen doubles per term in one CU's LDS); P (n, S) < 1; L not finite
+ * or <= 0; a NULL pointer.                                                                       */
+enum { DH_PARAM_GRAD_MAX_N = 1024, DH_N_PARAM_SENS = 14 };
+/* out[(i * P + p) * M + m], i = 0 the price and 1..13 the parameters, m in the caller's option
+ * order as in dh_surface_price.  Host arrays, synchronous.                                       */
+int dh_surface_param_sens(dh_ctx* ctx, const dh_surface* s, const double* params, int64_t P, int N,
+                          double L, double* out);
+/* The same over device pointers: enqueued on `stream` (hipStream_t; NULL = the context's) without
+ * synchronisation, no allocation; the same bits as dh_surface_param_sens.                        */
+int dh_surface_param_sens_dev(dh_ctx* ctx, const dh_surface* s, const double* d_params, int64_t P,
+                              int N, double L, double* d_out, void* stream);
+/* Option i under param set i: out[i_plane * n + i].  Host arrays, synchronous; the bits
+ * dh_surface_param_sens gives the same (set, option) pair.                                       */
+int dh_param_sens_pairs(dh_ctx* ctx, const double* params, const double* K, const double* T,
+                        const int8_t* is_call, int64_t n, int N, double L, double* out);
+/* The price objective (compute_loss, lbfgs_calibrator.py:118-177) of S unconstrained points
+ * x[S][13] against the surface's market prices, with its exact gradient in x, reduced on the
+ * device in a fixed order (one wave per set):
+ *     f[s] = sse / M + Feller,
+ *     g[s][i] = (2 / M) sum_m ((p_m - mkt_m) / mkt_m^2) dp_m/dtheta_i dtheta_i/dx_i + dFeller/dx_i
+ * with dtheta/dx = theta (exp-mapped parameters), 1 - rho^2 (the two correlations), 1 (mu_j), and
+ * the Feller term 1000 max(0, sigma^2 - 2 kappa theta) per factor differentiated where its slack
+ * is strictly positive (+2000 sigma^2 for sigma, -2000 kappa theta for each of kappa and theta),
+ * zero otherwise: on the kink itself this differs from dh_surface_fg's forward quotient.  A set
+ * with an invalid price (bad[s] > 0: NaN, +-inf or <= 0) gets f = 1e10 and g = 0, what the
+ * quotient of the constant 1e10 gives.  S0, r, N, L as in dh_surface_fg (q = 0).  Host arrays,
+ * synchronous.  DH_E_ARG also for a surface without market prices or options, and S0 or r not
+ * finite.                                                                                        */
+int dh_surface_loss_grad(dh_ctx* ctx, const dh_surface* s, const double* x, int S, double S0,
+                         double r, int N, double L, double* f, double* g, int32_t* bad);
+/* The same over device pointers, enqueued on `stream`; the same bits.  Its records and the
+ * [14][S][M] planes live in the context's one grow-only scratch buffer, so:
+ *   - ONE request in flight per context: a second dh_surface_loss_grad_dev (or the host form) on
+ *     the same context may be issued only on the same stream, or after the first has completed;
+ *     requests that are to overlap take a context each (dh_ctx_create on the same device);
+ *   - a request larger (S x M) than any earlier one on this context grows the buffer with hipFree
+ *     / hipMalloc, which synchronises the device and cannot be captured into a graph.  A request
+ *     no larger than an earlier one allocates nothing and does not synchronise: issue the largest
+ *     request once before capturing or timing.                                                   */
+int dh_surface_loss_grad_dev(dh_ctx* ctx, const dh_surface* s, const double* d_x, int S, double S0,
+                             double r, int N, double L, double* d_f, double* d_g, int32_t* d_bad,
+                             void* stream);
+
 /* ---- Black-Scholes implied volatility ----------------------------------------------------- */
 /* sigma[i] = the volatility whose Black-Scholes price of (S0[i], K[i], T[i], r[i], q[i],
  * is_call[i]) is price[i]; every array has n entries (structure of arrays), one GPU lane per quote.

@@ -2828,3 +2828,5 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
                              // variates): dh_host.h, dh_api.h
 #include "dh_lsm.h"          // American / Bermudan options by least-squares Monte Carlo: dh_mc.h
 #include "dh_greeks.h"       // analytic Greeks of the COS price: dh_host.h
+#include "dh_param_grad.h"   // analytic parameter sensitivities, loss + gradient: dh_greeks.h,
+                             // dh_loss_rows.h, dh_api.h

@@ -13,6 +13,9 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
     american_monte_carlo              (new: American and Bermudan options by least-squares Monte Carlo)
     greeks                            (new: analytic delta, gamma, dual delta and v0 vegas of the
                                        COS price, one pass; the module itself is dhcos/greeks.py)
+    parameter_sensitivities           (new: the price's analytic sensitivity to each of the 13 model
+                                       parameters, one pass; DoubleHestonJumpCalibrator(...,
+                                       gradient="analytic") fits with the exact loss gradient)
 
 All pricing arithmetic runs in libdhcos.so (hand-written gfx950 HIP kernels, C-ABI in
 include/dhcos.h); the native library is loaded on first use and there is no CPU fallback.
@@ -27,11 +30,13 @@ from .batch import BatchCalibrationResult, calibrate_batch
 from .montecarlo import MonteCarloResult, VarianceReducedResult, monte_carlo
 from .american import AmericanMonteCarloResult, american_monte_carlo
 from .greeks import Greeks, greeks
+from .param_sens import ParameterSensitivities, parameter_sensitivities
 from ._native import NativeError
 
 __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
            "generate_synthetic_calibrations", "implied_vol", "NativeError", "calibrate_batch",
            "BatchCalibrationResult", "monte_carlo", "MonteCarloResult",
            "VarianceReducedResult",
-           "american_monte_carlo", "AmericanMonteCarloResult", "greeks", "Greeks"]
+           "american_monte_carlo", "AmericanMonteCarloResult", "greeks", "Greeks",
+           "parameter_sensitivities", "ParameterSensitivities"]
 __version__ = "0.1.0"

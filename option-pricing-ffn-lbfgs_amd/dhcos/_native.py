@@ -44,6 +44,11 @@ LSM_MAX_GIB = 16               # DH_LSM_MAX_GIB: cap of the path store
 STAMPS_PER_BLOCK = 32          # kStamps of the DH_STAMPS build (csrc/dh_kernels.hip)
 # the planes of dh_surface_greeks / dh_greeks_pairs, in the order of the header's DH_GREEK_* enum
 GREEKS = ("price", "delta", "gamma", "dual_delta", "vega1", "vega2")
+# the planes of dh_surface_param_sens / dh_param_sens_pairs: the price, then the record's thirteen
+# model parameters (DH_N_PARAM_SENS planes); the longest series they take (DH_PARAM_GRAD_MAX_N)
+PARAM_SENS = ("price", "v1_0", "kappa1", "theta1", "sigma1", "rho1", "v2_0", "kappa2", "theta2",
+              "sigma2", "rho2", "lambda_j", "mu_j", "sigma_j")
+PARAM_GRAD_MAX_N = 1024
 
 _dp = C.POINTER(C.c_double)
 _i8p = C.POINTER(C.c_int8)
@@ -153,6 +158,13 @@ SIGNATURES = {
     "dh_surface_greeks": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp]),
     "dh_surface_greeks_dev": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp, _vp]),
     "dh_greeks_pairs": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _dbl, _vp]),
+    # ---- analytic parameter sensitivities, the loss and its gradient
+    "dh_surface_param_sens": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp]),
+    "dh_surface_param_sens_dev": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp, _vp]),
+    "dh_param_sens_pairs": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _dbl, _vp]),
+    "dh_surface_loss_grad": (_int, [_vp, _vp, _vp, _int, _dbl, _dbl, _int, _dbl, _vp, _vp, _vp]),
+    "dh_surface_loss_grad_dev": (_int, [_vp, _vp, _vp, _int, _dbl, _dbl, _int, _dbl, _vp, _vp,
+                                        _vp, _vp]),
     # ---- Black-Scholes implied volatility
     "dh_implied_vol": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dh_implied_vol_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
@@ -501,6 +513,19 @@ class Context(_Handle):
         with self._lock:
             _check(load().dh_greeks_pairs(self._h, _addr(params, n), _addr(K, n), _addr(T, n),
                                           _addr(ic, n), n, int(N), float(L), _addr(out, n)))
+        return out
+
+    def param_sens_pairs(self, params, K, T, is_call, N=128, L=10.0):
+        """dh_param_sens_pairs: the planes PARAM_SENS of option i under param record i
+        -> [14, n]."""
+        params = _records(params)
+        n = params.shape[0]
+        K, T = _f64(K).reshape(n), _f64(T).reshape(n)
+        ic = _flags(is_call, n)
+        out = np.empty((len(PARAM_SENS), n))
+        with self._lock:
+            _check(load().dh_param_sens_pairs(self._h, _addr(params, n), _addr(K, n), _addr(T, n),
+                                              _addr(ic, n), n, int(N), float(L), _addr(out, n)))
         return out
 
     def price_batch(self, params, K, T, is_call, N=128, L=10.0):
@@ -1076,6 +1101,45 @@ class Surface(_Handle):
         _check(load().dh_surface_greeks_dev(self.ctx.handle, self._h, _addr(d_params), int(P),
                                             int(N), float(L), _addr(d_out), _addr(stream)))
 
+    def param_sens(self, params, N=128, L=10.0):
+        """dh_surface_param_sens: the planes PARAM_SENS (the price, then its sensitivity to each of
+        the thirteen model parameters) of every option under every param row -> [14, P, M].
+        Partial derivatives of the COS series at a fixed truncation range (include/dhcos.h)."""
+        params = _records(params)
+        P = params.shape[0]
+        out = np.empty((len(PARAM_SENS), P, self.M))
+        with self.ctx._lock:
+            _check(load().dh_surface_param_sens(self.ctx.handle, self._h, _addr(params, P), P,
+                                                int(N), float(L), out.ctypes.data))
+        return out
+
+    def param_sens_dev(self, d_params: int, P: int, d_out: int, N=128, L=10.0, stream: int = 0):
+        """dh_surface_param_sens_dev: d_params [P, 16] in, d_out [14, P, M] out, enqueued on
+        stream."""
+        _check(load().dh_surface_param_sens_dev(self.ctx.handle, self._h, _addr(d_params), int(P),
+                                                int(N), float(L), _addr(d_out), _addr(stream)))
+
+    def loss_grad(self, X, S0, r, N=128, L=10.0):
+        """dh_surface_loss_grad: the price objective and its analytic gradient in the optimiser's
+        unconstrained x, one row of X [S, 13] each -> (f [S], g [S, 13], bad [S]); an invalid set
+        (bad > 0) has f = 1e10 and g = 0."""
+        X = _f64(X).reshape(-1, 13)
+        S = X.shape[0]
+        f, g, bad = np.empty(S), np.empty((S, 13)), np.empty(S, dtype=np.int32)
+        with self.ctx._lock:
+            _check(load().dh_surface_loss_grad(self.ctx.handle, self._h, _addr(X, S), S, float(S0),
+                                               float(r), int(N), float(L), f.ctypes.data,
+                                               g.ctypes.data, bad.ctypes.data))
+        return f, g, bad
+
+    def loss_grad_dev(self, d_x: int, S: int, S0, r, d_f: int, d_g: int, d_bad: int, N=128,
+                      L=10.0, stream: int = 0):
+        """dh_surface_loss_grad_dev: d_x [S, 13] in, d_f [S], d_g [S, 13], d_bad [S] (int32) out,
+        enqueued on stream."""
+        _check(load().dh_surface_loss_grad_dev(self.ctx.handle, self._h, _addr(d_x), int(S),
+                                               float(S0), float(r), int(N), float(L), _addr(d_f),
+                                               _addr(d_g), _addr(d_bad), _addr(stream)))
+
     def price_dev(self, d_params: int, P: int, d_out: int, N=128, L=10.0, stream: int = 0):
         _check(load().dh_surface_price_dev(self.ctx.handle, self._h, d_params, int(P), int(N),
                                            float(L), d_out, _addr(stream)))
@@ -1602,7 +1666,7 @@ __all__ = [
     "LIB_PATH", "SIGNATURES", "NativeError", "load", "runtime_shared_with_torch", "device_count",
     "resolve_device", "default_context", "PARAM_STRIDE", "MAX_N", "MAX_N_PER_TERM",
     "STRIKE_ABSOLUTE", "STRIKE_PCT_SPOT", "PATH_AUTO", "PATH_SPLIT", "PATH_FUSED", "PATH_GEN",
-    "FG_SLOTS", "STAMPS_PER_BLOCK", "GREEKS",
+    "FG_SLOTS", "STAMPS_PER_BLOCK", "GREEKS", "PARAM_SENS", "PARAM_GRAD_MAX_N",
     "Context", "Surface", "FgChannel", "pinned", "pinned_empty", "host_cache_trim",
     "LbOptions", "LbResult", "lb_batch_args", "iv_rows",
     "gen_draw", "GenDraw", "GEN_LOC_WORDS", "gen_locate", "gen_draw_located", "gen_sweep",

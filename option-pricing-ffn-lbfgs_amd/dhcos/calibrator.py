@@ -215,18 +215,42 @@ class DoubleHestonJumpCalibrator:
     """Calibrates the 13 Double-Heston + jump parameters to a list of market options."""
 
     objective = "price"        # a subclass that skips __init__ keeps the reference's objective
+    gradient = "fd"            # and SciPy's forward-difference gradient
 
     def __init__(self, spot: float, risk_free_rate: float, market_options: List[Dict], *,
                  N: int = 128, device=None, objective: str = "price", market_ivs=None,
-                 iv_weights=None):
+                 iv_weights=None, gradient: str = "fd"):
         """objective="price": the reference's relative price error.  objective="iv": the weighted
         mean squared error of the Black-Scholes vols, sum_m w_m (iv_model - iv_mkt)^2 / sum(w), with
         market_ivs the market's vols (default: the device inversion of the option prices at spot,
         rate and q = 0, formed with the surface) and iv_weights the w_m (default 1; 0 drops an
-        option).  A market vol that is not finite at a non-zero weight raises ValueError."""
+        option).  A market vol that is not finite at a non-zero weight raises ValueError.
+
+        gradient="fd" (the default): SciPy's forward differences, 14 loss evaluations per
+        function+gradient request, the reference's optimizer bit for bit.  gradient="analytic": the
+        loss and its exact gradient from one pass (dh_surface_loss_grad: the COS series
+        differentiated term by term at a fixed truncation range), one evaluation
+        per request and no quotient noise; the price objective and driver="scipy" only, N <= 1024,
+        and not with a subclass that replaces the loss.  The Feller penalty's derivative is taken
+        where its slack is strictly positive, so on the kink itself (the literature start) the
+        gradient differs from the forward quotient and that start may move where the "fd" run
+        stops at once."""
         if objective not in ("price", "iv"):
             raise ValueError(f"objective must be 'price' or 'iv', not {objective!r}")
+        if gradient not in ("fd", "analytic"):
+            raise ValueError(f"gradient must be 'fd' or 'analytic', not {gradient!r}")
+        if gradient == "analytic":
+            if objective != "price":
+                raise ValueError("gradient='analytic' differentiates the price objective only; "
+                                 "objective='iv' runs gradient='fd'")
+            if _custom_loss(self):
+                raise ValueError("gradient='analytic' needs the built-in loss: this subclass "
+                                 "replaces compute_loss or loss_batch (use gradient='fd')")
+            if int(N) != N or not 1 <= N <= _native.PARAM_GRAD_MAX_N:
+                raise ValueError("gradient='analytic': N must be a whole number in "
+                                 f"[1, {_native.PARAM_GRAD_MAX_N}], got {N!r}")
         self.objective = objective
+        self.gradient = gradient
         self.market_ivs = self.iv_weights = None
         if objective == "iv":
             M = len(market_options)
@@ -375,6 +399,8 @@ class DoubleHestonJumpCalibrator:
         request; the transforms by NumPy, fd_models) unless a subclass replaces loss_batch,
         whose values are then used the same way."""
         X0 = np.atleast_2d(np.asarray(X0, dtype=np.float64))
+        if self.gradient == "analytic":
+            return self._fg_analytic(X0)
         if self.objective == "iv":      # one request of the 14 S points, the difference on the host
             return fg_from_losses(self, X0)
         native = not _custom_loss(self)
@@ -384,13 +410,34 @@ class DoubleHestonJumpCalibrator:
         self.loss_evals += X0.shape[0] * (N_PARAMS + 1)
         return surf.fg(X0, self.spot, self.risk_free_rate, self.N, model=fd_models(X0))
 
+    def _fg_analytic(self, X0: np.ndarray):
+        """fg_batch under gradient="analytic": (f, g, low) of dh_surface_loss_grad, one loss
+        evaluation per row; low = f where the set is valid, inf where it is not (as the FD
+        request's smallest valid loss).  No market: NaN (np.mean([])); an option type the reference
+        cannot read: 1e10; the gradient zero in both."""
+        S = X0.shape[0]
+        self.loss_evals += S
+        surf = self._get_surface() if len(self.market_options) else None
+        if surf is None:
+            f = np.full(S, INVALID_LOSS if len(self.market_options) else np.nan)
+            return f, np.zeros((S, N_PARAMS)), np.full(S, np.inf)
+        f, g, bad = surf.loss_grad(X0, self.spot, self.risk_free_rate, self.N)
+        return f, g, np.where((bad > 0) | np.isnan(f), np.inf, f)
+
     def compute_loss(self, x: np.ndarray) -> float:
         """Relative MSE + Feller penalty (lbfgs_calibrator.py:118-177)."""
         return float(self.loss_batch(np.asarray(x, dtype=np.float64)[None, :N_PARAMS])[0])
 
     def compute_loss_and_grad(self, x: np.ndarray, eps: float = FD_ABS_STEP):
         """(f, g) exactly as SciPy's 2-point forward difference would form them, from one launch
-        of the 14 points (x and x + h e_i)."""
+        of the 14 points (x and x + h e_i); under gradient="analytic" the loss and its exact
+        gradient from one evaluation (eps is not used)."""
+        if self.gradient == "analytic":
+            f, g, low = self._fg_analytic(np.asarray(x, dtype=np.float64)[None, :N_PARAMS])
+            self.n_calls += 1
+            if low[0] < self.best_loss:
+                self.best_loss = low[0]
+            return f[0], g[0]
         X, dx = fd_request_points(x, eps)
         f = self.loss_batch(X)
         return f[0], (f[1:] - f[0]) / dx
@@ -469,6 +516,9 @@ class DoubleHestonJumpCalibrator:
         if driver == "device" and self.objective != "price":
             raise ValueError("driver='device' optimises the price objective only; "
                              "objective='iv' runs driver='scipy'")
+        if driver == "device" and self.gradient != "fd":
+            raise ValueError("driver='device' forms forward differences on the device; "
+                             "gradient='analytic' runs driver='scipy'")
         # draw every start's x0 in start order (the only consumer of the global RNG, :256)
         if x0s is None:
             x0s = self.start_points(multi_start, x0)
@@ -619,7 +669,8 @@ def _native_surface(cal, group_starts):
     if (not isinstance(cal, DoubleHestonJumpCalibrator)
             or cls.fg_batch is not DoubleHestonJumpCalibrator.fg_batch
             or _custom_loss(cal) or not len(cal.market_options)
-            or cal.objective != "price"):      # dh_surface_fg* form the price loss
+            or cal.objective != "price"        # dh_surface_fg* form the price loss
+            or cal.gradient != "fd"):          # and its FD quotients
         return None
     return cal._get_surface()
 
@@ -780,6 +831,8 @@ def _advance(cal, gens, states, order, outcomes):
     zero-copy points in, a spin-wait on the request's event, no per-call argument marshalling),
     else through cal.fg_batch; both give the same values (fg_batch is dh_surface_fg)."""
     launches = 0
+    # loss evaluations per request and start: the 14 FD points, or the analytic gradient's one
+    calls = 1 if getattr(cal, "gradient", "fd") == "analytic" else N_PARAMS + 1
     surf = _native_surface(cal, max(len(g) for g in order)) if order else None
     chan = None if surf is None else _native.FgChannel(surf, 0, max(len(g) for g in order),
                                                        cal.spot, cal.risk_free_rate, cal.N)
@@ -815,7 +868,7 @@ def _advance(cal, gens, states, order, outcomes):
                         continue
                 launches += 1
                 _consume(states, gens, pending, outcomes, ids, f0, G, lows,
-                         getattr(cal, "request_trace", None))
+                         getattr(cal, "request_trace", None), calls)
     finally:
         if busy:                       # unwinding with the slot's request in flight
             try:
@@ -825,15 +878,16 @@ def _advance(cal, gens, states, order, outcomes):
     cal.lockstep_launches = launches
 
 
-def _consume(states, gens, pending, outcomes, ids, f0, G, lows, trace=None):
+def _consume(states, gens, pending, outcomes, ids, f0, G, lows, trace=None,
+             calls=N_PARAMS + 1):
     """A request's results to its starts' generators (the bookkeeping of _advance); trace (a
-    list) gets each start's (start, x, f, g)."""
+    list) gets each start's (start, x, f, g); calls: loss evaluations per start and request."""
     for j, sid in enumerate(ids):
         if trace is not None:
             trace.append((sid, np.array(pending[sid], dtype=np.float64), float(f0[j]),
                           np.array(G[j], dtype=np.float64)))
         st = states[sid]
-        st.n_calls += N_PARAMS + 1
+        st.n_calls += calls
         if lows[j] < st.best_loss:
             st.best_loss = lows[j]
         try:
@@ -1019,6 +1073,9 @@ def run_starts_device(cal: DoubleHestonJumpCalibrator, x0s, maxiter: int):
     n = len(x0s)
     if getattr(cal, "objective", "price") != "price":
         raise ValueError("the device-resident L-BFGS-B optimises the price objective only")
+    if getattr(cal, "gradient", "fd") != "fd":
+        raise ValueError("the device-resident L-BFGS-B forms forward differences on the device; "
+                         "gradient='analytic' runs driver='scipy'")
     if n == 0:
         return []
     surf = cal._get_surface()

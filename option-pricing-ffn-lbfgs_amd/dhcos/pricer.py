@@ -156,6 +156,15 @@ class DoubleHeston:
                                        [resolve_call(self.option_type)], check_N(N))
         return Greeks.from_planes(out[:, 0])
 
+    def parameter_sensitivities(self, N=128):
+        """``ParameterSensitivities`` (the price and d price / d each of the 13 model parameters) of
+        this instance's option as scalars: analytic partial derivatives of ``pricing(N)``'s COS
+        series at a fixed truncation range (``dhcos.parameter_sensitivities``; N <= 1024)."""
+        from .param_sens import ParameterSensitivities, check_N
+        out = self._ctx().param_sens_pairs(self._record(), [float(self.K)], [float(self.T)],
+                                           [resolve_call(self.option_type)], check_N(N))
+        return ParameterSensitivities.from_planes(out[:, 0])
+
     def monte_carlo(self, n_paths=1 << 20, steps_per_year=64, seed=0, antithetic=False,
                     control_variate=False):
         """(price, stderr) of this instance's option by simulating the model's SDE
