@@ -451,6 +451,30 @@ int dh_surface_loss_grad(dh_ctx* ctx, const dh_surface* s, const double* x, int 
 int dh_surface_loss_grad_dev(dh_ctx* ctx, const dh_surface* s, const double* d_x, int S, double S0,
                              double r, int N, double L, double* d_f, double* d_g, int32_t* d_bad,
                              void* stream);
+/* The same against a market row per set: set s of x[S][13] is priced under
+ * spot[row[s]] and rate[row[s]] (q = 0) and held to the market prices mkt[row[s]][M], the caller's
+ * option order, of mkt [B][M].  Three stages: records and Feller penalties from x (dh_surface_fg's
+ * transform, each set's spot and rate from its row), the parameter planes, and a reduction of one
+ * wave per set -- lane l adds the surface's sorted options l, l + 64, ... uncontracted from 0.0,
+ * then the xor butterfly over the 64 lanes -- with dh_surface_loss_grad's f, g and bad, its invalid
+ * sets (f = 1e10, g = 0) and its one-sided Feller derivative.  A set's f and g depend on nothing
+ * but its own x and market row: not on S, B or the set's place in the call; with B = 1 and the
+ * surface's own market prices, spot and rate they are dh_surface_loss_grad's bits.  The surface
+ * needs no market prices of its own.  Host arrays, synchronous.  DH_E_ARG as dh_surface_loss_grad
+ * (N outside [1, DH_PARAM_GRAD_MAX_N], S < 1, L, an empty surface, a NULL pointer) and as
+ * dh_surface_loss_rows: B <= 0, a row outside [0, B), a spot that is not finite or not > 0, a rate
+ * that is not finite.                                                                            */
+int dh_surface_loss_grad_rows(dh_ctx* ctx, const dh_surface* s, const double* x, const double* mkt,
+                              const double* spot, const double* rate, const int32_t* row, int S,
+                              int B, int N, double L, double* f, double* g, int32_t* bad);
+/* The same over device pointers, enqueued on `stream`; the same bits.  d_mkt [B][M], d_spot [B],
+ * d_rate [B], d_row [S] with every row in [0, B) and every spot and rate valid (the caller's
+ * promise).  Scratch, the one request in flight per context and the growth rule are
+ * dh_surface_loss_grad_dev's.                                                                    */
+int dh_surface_loss_grad_rows_dev(dh_ctx* ctx, const dh_surface* s, const double* d_x,
+                                  const double* d_mkt, const double* d_spot, const double* d_rate,
+                                  const int32_t* d_row, int S, int N, double L, double* d_f,
+                                  double* d_g, int32_t* d_bad, void* stream);
 
 /* ---- Black-Scholes implied volatility ----------------------------------------------------- */
 /* sigma[i] = the volatility whose Black-Scholes price of (S0[i], K[i], T[i], r[i], q[i],
@@ -599,6 +623,25 @@ int dh_calibrate_lbfgs_batch_iv(dh_ctx* ctx, const dh_surface* s, const double* 
                                 const double* wgt, const double* spot, const double* rate, int B,
                                 const double* x0, const int32_t* market_of, int S, int N, double L,
                                 const dh_lb_options* opt, dh_lb_result* out, int32_t* n_launches);
+
+/* ---- many markets on one grid, with the analytic gradient (csrc/dh_lb_driver.h) */
+/* dh_calibrate_lbfgs_batch with the exact gradient of dh_surface_loss_grad_rows where that driver
+ * forms SciPy's forward quotient: a request is ONE point per start.  Every iteration is the
+ * parameter-plane launch over one record per live start, the rows reduction into f [live] and
+ * g [live][13], and one step launch, which hands (f, g) to the same L-BFGS-B state machine and
+ * writes each next record with its start's spot, rate, market row and Feller penalty.  The
+ * arguments, options, results, chunked enqueue, compaction and trace are
+ * dh_calibrate_lbfgs_batch's; n_calls counts one loss evaluation per request (n_calls == nfev),
+ * best_loss is the smallest valid f.  On the Feller kink the gradient is the one-sided rule of
+ * dh_surface_loss_grad, not the forward quotient's slope, so a start on it may move where the FD
+ * driver's stalls.  The planes' scratch is reserved once for all S starts before the first
+ * iteration.  A start's requests and results depend on nothing but its own x0 and market: not on
+ * B, S, the order of the markets or the chunk size.  DH_E_ARG as dh_calibrate_lbfgs_batch, and for
+ * N outside [1, DH_PARAM_GRAD_MAX_N] or L not finite or <= 0.                                    */
+int dh_calibrate_lbfgs_batch_grad(dh_ctx* ctx, const dh_surface* s, const double* mkt,
+                                  const double* spot, const double* rate, int B, const double* x0,
+                                  const int32_t* market_of, int S, int N, double L,
+                                  const dh_lb_options* opt, dh_lb_result* out, int32_t* n_launches);
 
 /* ---- building blocks (exposed for API parity with the reference's public methods) -------- */
 /* phi(u_j; tau) for one param set: DoubleHeston.characteristic_function (double_heston.py:48-97) */

@@ -2822,7 +2822,6 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
 #include "dh_iv.h"           // implied vols: dh_api.h
 #include "dh_iv_loss.h"      // the vol-space loss stages: dh_iv.h, dh_api.h
 #include "dh_loss_rows.h"    // per-set market rows: dh_iv_loss.h
-#include "dh_lb_driver.h"    // the device-resident L-BFGS-B: dh_api.h, dh_iv_loss.h, dh_loss_rows.h
 #include "dh_math_probe.h"   // the device math primitives one by one: dh_host.h
 #include "dh_mc.h"           // the Monte Carlo path pricer (includes dh_mc_vr.h, its control
                              // variates): dh_host.h, dh_api.h
@@ -2830,3 +2829,5 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
 #include "dh_greeks.h"       // analytic Greeks of the COS price: dh_host.h
 #include "dh_param_grad.h"   // analytic parameter sensitivities, loss + gradient: dh_greeks.h,
                              // dh_loss_rows.h, dh_api.h
+#include "dh_lb_driver.h"    // the device-resident L-BFGS-B: dh_api.h, dh_iv_loss.h, dh_loss_rows.h,
+                             // dh_param_grad.h

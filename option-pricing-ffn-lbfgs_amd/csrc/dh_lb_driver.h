@@ -1,9 +1,10 @@
 // dh_lb_driver.h -- the device-resident multi-start L-BFGS-B driver (dh_calibrate_lbfgs,
-// dh_calibrate_lbfgs_batch, dh_calibrate_lbfgs_batch_iv, dh_ctx_set_lb_trace,
-// dh_ctx_read_lb_trace): the step kernel, its launch and the host loop.  Included by
-// dh_kernels.hip after the loss stages (dh_iv_loss.h, dh_loss_rows.h), whose launches the host
-// loop calls; kInvalidLoss, kFdStep, kSqrtEps and lb_transform, which the one-shot entry points
-// share, stay in dh_kernels.hip.  DESIGN.md 3.8, 3.12-3.14.
+// dh_calibrate_lbfgs_batch, dh_calibrate_lbfgs_batch_iv, dh_calibrate_lbfgs_batch_grad,
+// dh_ctx_set_lb_trace, dh_ctx_read_lb_trace): the step kernel, its launch and the host loop.
+// Included by dh_kernels.hip after the loss stages (dh_iv_loss.h, dh_loss_rows.h,
+// dh_param_grad.h), whose launches the host loop calls; kInvalidLoss, kFdStep, kSqrtEps and
+// lb_transform, which the one-shot entry points share, stay in dh_kernels.hip.  DESIGN.md 3.8,
+// 3.12-3.14, 3.19.
 //
 // Nothing here is contracted into FMAs: the step kernel must compute the bits of the CPU build
 // of dh_lbfgs.h (tests/native/lb_host.cpp).
@@ -147,6 +148,12 @@ struct LbArgs {
     // dh_calibrate_lbfgs_batch_iv only (lb_step_kernel<., true, true>), appended again: each
     // start's loss divisor, its market's weight sum (dh_loss_rows.h)
     const double* div_of;      // [S]
+    // dh_calibrate_lbfgs_batch_grad only (lb_step_kernel<., true, false, true>), appended again:
+    // the analytic gradient of the last request [n_live][13] (its loss, Feller included, is sse
+    // [n_live]) and the Feller penalty of each next record [n_live] (dh_param_grad.h's rows
+    // reduction writes the one and reads the other)
+    const double* grad;
+    double* pen_out;
 };
 static_assert(std::is_standard_layout<LbArgs>::value, "lb_live_inline reads LbArgs by offset");
 
@@ -231,6 +238,29 @@ __device__ void lb_emit(const WaveCore& c, WaveVec& dx, WaveVec& pen, double* pb
     }
 }
 
+// The analytic-gradient driver's request (dh_calibrate_lbfgs_batch_grad): the one record of xe, no
+// bumps and no dx.  Lane i < 13 maps x_i to its model param and writes it; lanes 13..15 write the
+// start's spot, its rate and q = 0; lane 0 writes the set's market row and the record's Feller
+// penalty, x_records_kernel's expression, which the rows reduction adds to the loss.
+__device__ void lb_emit_grad(const WaveCore& c, WaveVec& dx, WaveVec& pen, double* pb,
+                             const LbArgs& A, int slot, int lane, int sidx) {
+    dx.v = 0.0;
+    if (lane < dhlb::kN) pb[lane] = lb_transform(lane, c.xe.v);
+    __syncthreads();
+    const double v1 = pb[3] * pb[3] - 2.0 * pb[1] * pb[2];
+    const double v2 = pb[8] * pb[8] - 2.0 * pb[6] * pb[7];
+    pen.v = 1000.0 * ((v1 > 0.0 ? v1 : 0.0) + (v2 > 0.0 ? v2 : 0.0));
+    double* out = A.rec + (size_t)slot * DH_PARAM_STRIDE;
+    if (lane < dhlb::kN) out[lane] = pb[lane];
+    else if (lane == 13) out[13] = A.spot_of[sidx];
+    else if (lane == 14) out[14] = A.rate_of[sidx];
+    else if (lane == 15) out[15] = 0.0;
+    if (lane == 0) {
+        A.row[slot] = A.market_of[sidx];
+        A.pen_out[slot] = pen.v;
+    }
+}
+
 // The loss hand-off's sum of one param set's nt tile partials (task_loss: lane l adds tiles l,
 // l + 64, ... in order, then an xor butterfly), formed by one lane: leaf l as that lane's sum,
 // then the butterfly's tree (level w adds leaves w apart).  Leaves past nt are +0.0 and adding
@@ -276,7 +306,10 @@ __device__ __forceinline__ void lb_tile_tree(const double* ps, int nt, double& s
 // two kB = false builds are dh_calibrate_lbfgs's, unchanged.  kIv (with kB):
 // dh_calibrate_lbfgs_batch_iv's builds -- the request's sse is dh_loss_rows.h's vol reduction and
 // the loss divides it by the start's weight sum (div_of) where the price objective divides by M.
-template <bool kPre, bool kB = false, bool kIv = false>
+// kG (with kB): dh_calibrate_lbfgs_batch_grad's builds -- the request is one point, its loss (sse)
+// and gradient (grad) come finished from dh_param_grad.h's rows reduction, and the next request
+// is the one record of lb_emit_grad.
+template <bool kPre, bool kB = false, bool kIv = false, bool kG = false>
 __global__ __launch_bounds__(64) void lb_step_kernel(
     LbSlot* __restrict__ h_states, const double* __restrict__ h_part, int h_ntiles, int h_mode,
     int h_part_mode, int h_l0, int h_l1, int h_l2, int h_l3, LbArgs A_) {
@@ -301,6 +334,7 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
     WaveVec dx, pen;
     double req_sse = 0.0;
     int req_bad = 0;
+    [[maybe_unused]] double req_g = 0.0;
     if (h_mode == 0) {
         c.s = dhlb::LbScalars{};
         const WaveVec z{0.0};
@@ -314,7 +348,12 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
     } else {
         // every load is issued before any is used (one memory round trip): the finished request's
         // loss terms, the pair memory, the vectors and the scalars
-        if (h_mode == 1 && h_part_mode) {
+        if constexpr (kG) {
+            if (h_mode == 1) {
+                req_sse = A.sse[slot];
+                req_g = (lane & 15) < dhlb::kN ? A.grad[(size_t)slot * dhlb::kN + (lane & 15)] : 0.0;
+            }
+        } else if (h_mode == 1 && h_part_mode) {
             // the loss hand-off's sum (task_loss), formed by lane t of every row for point t
             // (lb_tile_tree: the same additions, so the same bits).  Measured alternatives, all
             // slower: staging the request's contiguous partials through LDS with coalesced loads
@@ -362,19 +401,28 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
     if (h_mode == 1) {
         t_load = lb_clock();
         double f = __builtin_huge_val();
-        if constexpr (kIv) {
+        if constexpr (kG) {
+            // the reduction's loss: Feller included, 1e10 (and a zero gradient) at an invalid price
+            f = req_sse;
+            c.s.n_calls += 1;
+            if (f == f && f != kInvalidLoss && f < c.s.best_loss) c.s.best_loss = f;
+            c.s.fe = f;
+            c.ge.v = req_g;
+        } else if constexpr (kIv) {
             if ((lane & 15) < dhlb::kPts)
                 f = req_bad > 0 ? kInvalidLoss : req_sse / A.div_of[sidx] + pen.v;
         } else {
             if ((lane & 15) < dhlb::kPts) f = req_bad > 0 ? kInvalidLoss : req_sse / (double)A.M + pen.v;
         }
-        if (lane < dhlb::kLanes) fl[lane] = f;
-        __syncthreads();
-        const double lo = row_min((f == f && f != kInvalidLoss) ? f : __builtin_huge_val());
-        c.s.n_calls += dhlb::kPts;
-        if (lo < c.s.best_loss) c.s.best_loss = lo;
-        c.s.fe = fl[0];
-        c.ge.v = (lane & 15) < dhlb::kN ? (fl[(lane & 15) + 1] - fl[0]) / dx.v : 0.0;
+        if constexpr (!kG) {
+            if (lane < dhlb::kLanes) fl[lane] = f;
+            __syncthreads();
+            const double lo = row_min((f == f && f != kInvalidLoss) ? f : __builtin_huge_val());
+            c.s.n_calls += dhlb::kPts;
+            if (lo < c.s.best_loss) c.s.best_loss = lo;
+            c.s.fe = fl[0];
+            c.ge.v = (lane & 15) < dhlb::kN ? (fl[(lane & 15) + 1] - fl[0]) / dx.v : 0.0;
+        }
         if (A.trace) {
             unsigned long long k = 0;
             if (lane == 0) k = atomicAdd(A.trace_n, 1ull);
@@ -383,7 +431,7 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
                 tr = A.trace + k * kLbTrace;
                 if (lane == 0) {
                     tr[0] = sidx;
-                    tr[1] = c.s.n_calls / dhlb::kPts - 1;
+                    tr[1] = c.s.n_calls / (kG ? 1 : dhlb::kPts) - 1;
                     tr[2] = c.s.fe;
                     if constexpr (kB) tr[3 + 2 * dhlb::kN] = A.market_of[sidx];
                 }
@@ -404,7 +452,11 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
             atomicSub(A.live_count, 1);
         }
     }
-    if (need) lb_emit<kB>(c, dx, pen, pb, pp, A, slot, lane, sidx);
+    if constexpr (kG) {
+        if (need) lb_emit_grad(c, dx, pen, pb, A, slot, lane, sidx);
+    } else {
+        if (need) lb_emit<kB>(c, dx, pen, pb, pp, A, slot, lane, sidx);
+    }
     __syncthreads();
     [[maybe_unused]] const unsigned long long t_emit = lb_clock();
     {   // every LDS read before the first store (one LDS round trip, not one per store)
@@ -437,13 +489,15 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
 
 // One objective's step launch: the kPre build where the (inline) live list fits the leading
 // arguments, the in-argument / in-memory list's build otherwise.
-template <bool kB, bool kIv>
+template <bool kB, bool kIv, bool kG = false>
 int launch_lb_step_as(hipStream_t st, const LbArgs& A, int n_live) {
-    static_assert(kB || !kIv, "the vol objective is the batch driver's only");
+    static_assert(kB || !(kIv || kG), "the vol objective and the analytic gradient are the batch "
+                                      "driver's only");
     const bool pre = A.n_inline && n_live <= kLbPre;
     int l[kLbPre] = {0, 0, 0, 0};
     for (int i = 0; pre && i < n_live; ++i) l[i] = A.live_inline[i];
-    const auto step = pre ? lb_step_kernel<true, kB, kIv> : lb_step_kernel<false, kB, kIv>;
+    const auto step =
+        pre ? lb_step_kernel<true, kB, kIv, kG> : lb_step_kernel<false, kB, kIv, kG>;
     hipLaunchKernelGGL(step, dim3((unsigned)n_live), dim3(64), 0, st, A.states, A.part_sse,
                        A.n_tiles, A.mode, A.part_mode, l[0], l[1], l[2], l[3], A);
     HIP_TRY(hipGetLastError());
@@ -451,7 +505,8 @@ int launch_lb_step_as(hipStream_t st, const LbArgs& A, int n_live) {
 }
 
 int launch_lb_step(hipStream_t st, const LbArgs& A, int n_live, bool batch = false,
-                   bool iv = false) {
+                   bool iv = false, bool grad = false) {
+    if (batch && grad) return launch_lb_step_as<true, false, true>(st, A, n_live);
     if (batch && iv) return launch_lb_step_as<true, true>(st, A, n_live);
     if (batch) return launch_lb_step_as<true, false>(st, A, n_live);
     return launch_lb_step_as<false, false>(st, A, n_live);
@@ -469,6 +524,8 @@ struct LbBatch {
     // market's weight sum [B] (null: the price objective)
     const double* iv_wgt = nullptr;
     const double* iv_wsum = nullptr;
+    // dh_calibrate_lbfgs_batch_grad: one analytic loss + gradient request per iteration
+    bool grad = false;
 };
 
 }  // namespace
@@ -476,6 +533,8 @@ struct LbBatch {
 // dh_calibrate_lbfgs (bt null: one market, the surface's, through the fused loss launches) and
 // dh_calibrate_lbfgs_batch (bt: a market per start, through price + dh_loss_rows.h's reduction)
 // and dh_calibrate_lbfgs_batch_iv (bt with weights: through price + dh_loss_rows.h's vol one)
+// and dh_calibrate_lbfgs_batch_grad (bt with grad: one record per start through dh_param_grad.h's
+// planes and rows reduction)
 static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, double S0, double r,
                   int N, double L, const dh_lb_options* opt, dh_lb_result* out,
                   int32_t* n_launches, const LbBatch* bt) {
@@ -484,6 +543,12 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
     if (s->M == 0) return fail(DH_E_ARG, "empty market (the loss is NaN; no optimisation)");
     int rc = check_N(N);
     if (rc) return rc;
+    const bool grad = bt && bt->grad;
+    if (grad && N > DH_PARAM_GRAD_MAX_N)
+        return fail(DH_E_ARG, "N must be in [1, " + std::to_string(DH_PARAM_GRAD_MAX_N) +
+                                  "] under the analytic gradient, got " + std::to_string(N));
+    if (grad && (!std::isfinite(L) || !(L > 0.0)))
+        return fail(DH_E_ARG, "L must be finite and > 0");
     if (S < 0) return fail(DH_E_ARG, "S < 0");
     if (opt->maxiter < 0 || opt->maxfun < 0 || opt->maxls < 1)   // SciPy: maxls must be > 0
         return fail(DH_E_ARG, "maxiter and maxfun must be >= 0, maxls >= 1");
@@ -532,7 +597,10 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
         const size_t mb = (size_t)bt->B * M * 8;
         HIP_TRY(ctx->rows_mkt.reserve(mb));
         HIP_TRY(ctx->rows_row.reserve(npts * 4));
-        HIP_TRY(ctx->lb_prices.reserve(npts * M * 8));
+        if (grad)   // once, for all S starts: the gradients [S][16], penalties [S], planes [14][S][M]
+            HIP_TRY(ctx->pg_scratch.reserve(dhpg::loss_grad_scratch(S, M)));
+        else
+            HIP_TRY(ctx->lb_prices.reserve(npts * M * 8));
         HIP_TRY(ctx->lb_spot.reserve((size_t)S * 8));
         HIP_TRY(ctx->lb_rate.reserve((size_t)S * 8));
         HIP_TRY(ctx->lb_mof.reserve((size_t)S * 4));
@@ -603,12 +671,19 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
     const bool batch = bt != nullptr;
     const bool iv = batch && bt->iv_wgt != nullptr;
     A.div_of = iv ? (const double*)ctx->lb_div.ptr : nullptr;
+    // dh_surface_loss_grad_dev's scratch layout with the gradients where it keeps its records (the
+    // driver's records are lb_rec, one per live start)
+    double* const d_grad = grad ? (double*)ctx->pg_scratch.ptr : nullptr;
+    double* const d_pen = grad ? d_grad + (size_t)S * DH_PARAM_STRIDE : nullptr;
+    double* const d_planes = grad ? d_pen + S : nullptr;
+    A.grad = d_grad;
+    A.pen_out = d_pen;
     auto set_inline = [&](const int* lst, int n) {
         A.n_inline = n <= kLbInline ? 1 : 0;
         for (int i = 0; i < kLbInline; ++i) A.live_inline[i] = i < n && A.n_inline ? lst[i] : 0;
     };
     set_inline(h_live[0], S);
-    rc = launch_lb_step(st, A, S, batch, iv);
+    rc = launch_lb_step(st, A, S, batch, iv, grad);
     if (rc) return rc;
 
     // Chunks of `chunk` iterations (loss launch(es) + step launch) are enqueued two ahead of the
@@ -626,6 +701,19 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
         A.mode = 1;
         for (int c = 0; c < chunk; ++c) {
             int e;
+            if (grad) {
+                // the planes of the live starts' records, then each set's loss and gradient
+                // against its start's market row; the step reads them finished
+                e = dhpg::loss_grad_rows_launch(ctx, s, A.rec, d_pen,
+                                                (const double*)ctx->rows_mkt.ptr, A.row, n_live, N,
+                                                L, d_planes, (double*)A.sse, d_grad, (int*)A.bad,
+                                                st, A.live_count);
+                if (e) return e;
+                e = launch_lb_step(st, A, n_live, true, false, true);
+                if (e) return e;
+                ++launches;
+                continue;
+            }
             if (batch) {
                 // prices of the 14 x live records, then each set against its start's market row
                 // (the rows the step kernel wrote beside the records)
@@ -701,7 +789,7 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
                                        hipMemcpyHostToDevice, st));
             }
             A.mode = 2;
-            rc = launch_lb_step(st, A, n_live, batch, iv);
+            rc = launch_lb_step(st, A, n_live, batch, iv, grad);
             if (rc) return rc;
         }
         rc = enqueue_chunk(k + 2);
@@ -763,6 +851,18 @@ extern "C" int dh_calibrate_lbfgs_batch_iv(dh_ctx* ctx, const dh_surface* s, con
     LbBatch bt{mkt_iv, spot, rate, B, market_of};
     bt.iv_wgt = w.data();
     bt.iv_wsum = wsum.data();
+    return lb_run(ctx, s, x0, S, 0.0, 0.0, N, L, opt, out, n_launches, &bt);
+}
+
+// The price objective with its analytic gradient: one request per start and iteration
+// (dh_param_grad.h's planes and rows reduction) where dh_calibrate_lbfgs_batch prices fourteen.
+extern "C" int dh_calibrate_lbfgs_batch_grad(dh_ctx* ctx, const dh_surface* s, const double* mkt,
+                                             const double* spot, const double* rate, int B,
+                                             const double* x0, const int32_t* market_of, int S,
+                                             int N, double L, const dh_lb_options* opt,
+                                             dh_lb_result* out, int32_t* n_launches) {
+    LbBatch bt{mkt, spot, rate, B, market_of};
+    bt.grad = true;
     return lb_run(ctx, s, x0, S, 0.0, 0.0, N, L, opt, out, n_launches, &bt);
 }
 

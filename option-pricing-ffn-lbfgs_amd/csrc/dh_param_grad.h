@@ -1,7 +1,9 @@
 // dh_param_grad.h -- analytic sensitivities of the COS price to the thirteen model parameters, and
 // the calibration loss with its exact gradient (dh_surface_param_sens*, dh_param_sens_pairs,
-// dh_surface_loss_grad*).  Included by dh_kernels.hip after dh_greeks.h; needs the
-// kernels' helpers (xor_sum, option_logk), dh_host.h and dh_api.h's x_records_kernel.
+// dh_surface_loss_grad*, and against a market row per set dh_surface_loss_grad_rows*; DESIGN.md
+// 3.18, 3.19).  Included by dh_kernels.hip after dh_greeks.h and ahead of the L-BFGS-B driver
+// (dh_lb_driver.h); needs the kernels' helpers (xor_sum, option_logk), dh_host.h, dh_loss_rows.h
+// and dh_api.h's x_records_kernel.
 //
 // Definition.  In dh_greeks.h's notation (xK = log(K / S0), [a, b] = truncationRange(L), u_k =
 // k pi / (b - a), w_k = phi(u_k) e^{-i u_k a}, price = e^{-rT} sum'_{k < N} Re(w_k) V_k), for a
@@ -464,13 +466,14 @@ int check_args(const dh_ctx* ctx, int64_t count, const char* count_name, int N, 
 // of the surface's *sorted* options l, l + 64, ... in that order (planes read at the option's place
 // in the caller's order, perm[m]); then the xor butterfly over the 64 lanes.  Nothing is contracted.
 // The order is a function of M and the surface's option sort alone.
-__global__ __launch_bounds__(kBlockRows) void loss_grad_kernel(
+// mkt: the set's market prices, in the surface's sorted order (kCaller false: the surface's own)
+// or in the caller's option order (kCaller true: a market row, read at perm[m]).
+template <bool kCaller>
+__device__ __forceinline__ void loss_grad_wave(
     const double* __restrict__ planes, const double* __restrict__ rec,
     const double* __restrict__ pen, const double* __restrict__ mkt, const int* __restrict__ perm,
-    int M, int64_t S, double* __restrict__ f, double* __restrict__ g, int* __restrict__ n_bad) {
-    const int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (s >= S) return;                              // whole waves: s is uniform across a wave
+    int M, int64_t S, int64_t s, int lane, double* __restrict__ f, double* __restrict__ g,
+    int* __restrict__ n_bad) {
     const int64_t plane = S * (int64_t)M;
     const double* p = planes + s * M;
     double acc = 0.0, gs[kPlanes - 1];
@@ -481,7 +484,7 @@ __global__ __launch_bounds__(kBlockRows) void loss_grad_kernel(
         const int m = m0 + lane;
         if (m < M) {
             const int c = perm[m];
-            const double pr = p[c], mm = mkt[m];
+            const double pr = p[c], mm = mkt[kCaller ? c : m];
             const double rel = (pr - mm) / mm;
             acc = acc + rel * rel;
             bad += (pr != pr || isinf(pr) || pr <= 0.0) ? 1 : 0;
@@ -524,6 +527,72 @@ __global__ __launch_bounds__(kBlockRows) void loss_grad_kernel(
     }
 }
 
+__global__ __launch_bounds__(kBlockRows) void loss_grad_kernel(
+    const double* __restrict__ planes, const double* __restrict__ rec,
+    const double* __restrict__ pen, const double* __restrict__ mkt, const int* __restrict__ perm,
+    int M, int64_t S, double* __restrict__ f, double* __restrict__ g, int* __restrict__ n_bad) {
+    const int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (s >= S) return;                              // whole waves: s is uniform across a wave
+    loss_grad_wave<false>(planes, rec, pen, mkt, perm, M, S, s, lane, f, g, n_bad);
+}
+
+// ---- the same against a market row per set (dh_surface_loss_grad_rows*, the analytic batch
+// driver's reduction) ---------------------------------------------------------------
+// x_records_kernel (dh_kernels.hip) with each set's spot and rate taken from its market row: the
+// same transform and Feller expressions, so the same records and penalties for the same inputs.
+__global__ void x_records_rows_kernel(const double* __restrict__ x, int S,
+                                      const double* __restrict__ spot,
+                                      const double* __restrict__ rate, const int* __restrict__ row,
+                                      double* __restrict__ rec, double* __restrict__ pen) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    double p[dhlb::kN];
+#pragma unroll
+    for (int i = 0; i < dhlb::kN; ++i) p[i] = lb_transform(i, x[(size_t)s * dhlb::kN + i]);
+    const double v1 = p[3] * p[3] - 2.0 * p[1] * p[2];
+    const double v2 = p[8] * p[8] - 2.0 * p[6] * p[7];
+    pen[s] = 1000.0 * ((v1 > 0.0 ? v1 : 0.0) + (v2 > 0.0 ? v2 : 0.0));
+    double* out = rec + (size_t)s * DH_PARAM_STRIDE;
+#pragma unroll
+    for (int i = 0; i < dhlb::kN; ++i) out[i] = p[i];
+    const int b = row[s];
+    out[13] = spot[b];
+    out[14] = rate[b];
+    out[15] = 0.0;
+}
+
+// loss_grad_kernel's wave against row[s] of mkt [B][M] (the caller's option order): the same sums
+// in the same order, so with B = 1 and the surface's own market prices the same bits.  live_count:
+// the device-resident driver's count of unfinished starts (the launch is a no-op at 0), or null.
+__global__ __launch_bounds__(kBlockRows) void loss_grad_rows_kernel(
+    const double* __restrict__ planes, const double* __restrict__ rec,
+    const double* __restrict__ pen, const double* __restrict__ mkt, const int* __restrict__ row,
+    const int* __restrict__ perm, int M, int64_t S, const int* __restrict__ live_count,
+    double* __restrict__ f, double* __restrict__ g, int* __restrict__ n_bad) {
+    if (live_count && __builtin_amdgcn_readfirstlane(*live_count) <= 0) return;
+    const int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (s >= S) return;                              // whole waves: s is uniform across a wave
+    loss_grad_wave<true>(planes, rec, pen, mkt + (int64_t)row[s] * M, perm, M, S, s, lane, f, g,
+                         n_bad);
+}
+
+// Stages 2 and 3 of a rows request over records already on the device: param_grad_kernel into
+// d_planes [14][S][M], then the rows reduction.  The analytic batch driver's iteration.
+int loss_grad_rows_launch(dh_ctx* ctx, const dh_surface* s, const double* d_rec,
+                          const double* d_pen, const double* d_mkt, const int* d_row, int S, int N,
+                          double L, double* d_planes, double* d_f, double* d_g, int* d_bad,
+                          hipStream_t st, const int* live_count) {
+    const int rc = launch_param_grad(ctx, surface_args(s, d_rec, S, N, L, d_planes), S, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loss_grad_rows_kernel, dim3(rows_grid(S)), dim3(kBlockRows), 0, st,
+                       (const double*)d_planes, d_rec, d_pen, d_mkt, d_row, (const int*)s->perm,
+                       s->M, (int64_t)S, live_count, d_f, d_g, d_bad);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+
 // scratch of a loss_grad request in the context's buffer: records [S][16], penalties [S], planes
 // [14][S][M]
 size_t loss_grad_scratch(int S, int M) {
@@ -539,6 +608,15 @@ int check_loss_grad(const dh_ctx* ctx, const dh_surface* s, int S, double S0, do
     if (!s->has_mkt) return fail(DH_E_ARG, "surface has no market prices");
     if (!std::isfinite(S0) || !(S0 > 0.0)) return fail(DH_E_ARG, "S0 must be finite and > 0");
     if (!std::isfinite(r)) return fail(DH_E_ARG, "r must be finite");
+    return DH_OK;
+}
+
+// the rows forms: the surface needs no market prices of its own
+int check_loss_grad_rows(const dh_ctx* ctx, const dh_surface* s, int S, int N, double L) {
+    int rc = check_args(ctx, S, "S", N, L);
+    if (rc) return rc;
+    if (!s) return fail(DH_E_ARG, "surface is null");
+    if (s->M == 0) return fail(DH_E_ARG, "surface is empty (the loss is NaN)");
     return DH_OK;
 }
 
@@ -673,6 +751,89 @@ extern "C" int dh_surface_loss_grad(dh_ctx* ctx, const dh_surface* s, const doub
     int32_t* d_bad = (int32_t*)(d_g + (size_t)S * kN);
     HIP_TRY(hipMemcpyAsync(d_x, x, xb, hipMemcpyHostToDevice, st));
     rc = dh_surface_loss_grad_dev(ctx, s, d_x, S, S0, r, N, L, d_f, d_g, d_bad, st);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(f, d_f, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(g, d_g, xb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(bad, d_bad, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DH_OK;
+}
+
+extern "C" int dh_surface_loss_grad_rows_dev(dh_ctx* ctx, const dh_surface* s, const double* d_x,
+                                             const double* d_mkt, const double* d_spot,
+                                             const double* d_rate, const int32_t* d_row, int S,
+                                             int N, double L, double* d_f, double* d_g,
+                                             int32_t* d_bad, void* stream) {
+    int rc = dhpg::check_loss_grad_rows(ctx, s, S, N, L);
+    if (rc) return rc;
+    if (!d_x) return fail(DH_E_ARG, "x is null");
+    if (!d_mkt) return fail(DH_E_ARG, "mkt is null");
+    if (!d_spot) return fail(DH_E_ARG, "spot is null");
+    if (!d_rate) return fail(DH_E_ARG, "rate is null");
+    if (!d_row) return fail(DH_E_ARG, "row is null");
+    if (!d_f) return fail(DH_E_ARG, "f is null");
+    if (!d_g) return fail(DH_E_ARG, "g is null");
+    if (!d_bad) return fail(DH_E_ARG, "bad is null");
+    DeviceScope dev_scope(ctx->device);
+    if (dev_scope.rc) return dev_scope.rc;
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    // dh_surface_loss_grad_dev's scratch and layout: records, penalties, planes
+    HIP_TRY(ctx->pg_scratch.reserve(dhpg::loss_grad_scratch(S, s->M)));
+    double* d_rec = (double*)ctx->pg_scratch.ptr;
+    double* d_pen = d_rec + (size_t)S * DH_PARAM_STRIDE;
+    double* d_planes = d_pen + S;
+    hipLaunchKernelGGL(dhpg::x_records_rows_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256),
+                       0, st, d_x, S, d_spot, d_rate, (const int*)d_row, d_rec, d_pen);
+    HIP_TRY(hipGetLastError());
+    return dhpg::loss_grad_rows_launch(ctx, s, d_rec, d_pen, d_mkt, (const int*)d_row, S, N, L,
+                                       d_planes, d_f, d_g, (int*)d_bad, st, nullptr);
+}
+
+extern "C" int dh_surface_loss_grad_rows(dh_ctx* ctx, const dh_surface* s, const double* x,
+                                         const double* mkt, const double* spot,
+                                         const double* rate, const int32_t* row, int S, int B,
+                                         int N, double L, double* f, double* g, int32_t* bad) {
+    int rc = dhpg::check_loss_grad_rows(ctx, s, S, N, L);
+    if (rc) return rc;
+    if (!x) return fail(DH_E_ARG, "x is null");
+    if (!mkt) return fail(DH_E_ARG, "mkt is null");
+    if (!spot) return fail(DH_E_ARG, "spot is null");
+    if (!rate) return fail(DH_E_ARG, "rate is null");
+    if (!row) return fail(DH_E_ARG, "row is null");
+    if (!f) return fail(DH_E_ARG, "f is null");
+    if (!g) return fail(DH_E_ARG, "g is null");
+    if (!bad) return fail(DH_E_ARG, "bad is null");
+    rc = check_rows(row, S, B);
+    if (rc) return rc;
+    for (int b = 0; b < B; ++b) {
+        if (!std::isfinite(spot[b]) || !(spot[b] > 0.0))
+            return fail(DH_E_ARG, "spot " + std::to_string(b) + " is not finite or not > 0");
+        if (!std::isfinite(rate[b]))
+            return fail(DH_E_ARG, "rate " + std::to_string(b) + " is not finite");
+    }
+    DeviceScope dev_scope(ctx->device);
+    if (dev_scope.rc) return dev_scope.rc;
+    constexpr int kN = dhpg::kPlanes - 1;
+    const size_t xb = (size_t)S * kN * 8, mb = (size_t)B * s->M * 8;
+    hipStream_t st = ctx->stream;
+    // x [S][13], then f [S], g [S][13], spot [B], rate [B], bad [S]
+    HIP_TRY(ctx->pg_io.reserve(2 * xb + (size_t)S * 16 + (size_t)B * 16));
+    HIP_TRY(ctx->rows_mkt.reserve(mb));
+    HIP_TRY(ctx->rows_row.reserve((size_t)S * 4));
+    double* d_x = (double*)ctx->pg_io.ptr;
+    double* d_f = d_x + (size_t)S * kN;
+    double* d_g = d_f + S;
+    double* d_spot = d_g + (size_t)S * kN;
+    double* d_rate = d_spot + B;
+    int32_t* d_bad = (int32_t*)(d_rate + B);
+    HIP_TRY(hipMemcpyAsync(d_x, x, xb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_spot, spot, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_rate, rate, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->rows_mkt.ptr, mkt, mb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->rows_row.ptr, row, (size_t)S * 4, hipMemcpyHostToDevice, st));
+    rc = dh_surface_loss_grad_rows_dev(ctx, s, d_x, (const double*)ctx->rows_mkt.ptr, d_spot,
+                                       d_rate, (const int32_t*)ctx->rows_row.ptr, S, N, L, d_f,
+                                       d_g, d_bad, st);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(f, d_f, (size_t)S * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(g, d_g, xb, hipMemcpyDeviceToHost, st));

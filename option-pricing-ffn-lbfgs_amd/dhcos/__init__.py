@@ -7,7 +7,8 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
     CalibrationResult
     generate_synthetic_calibrations   src/data/synthetic_generator.py
     implied_vol                       (new: Black-Scholes implied volatility of prices)
-    calibrate_batch                   (new: many markets on one option grid, calibrated together)
+    calibrate_batch                   (new: many markets on one option grid, calibrated together;
+                                       gradient="analytic" runs them on the exact loss gradient)
     monte_carlo                       (new: path pricing of European, Asian and barrier options,
                                        with antithetic pairs and COS-priced control variates)
     american_monte_carlo              (new: American and Bermudan options by least-squares Monte Carlo)

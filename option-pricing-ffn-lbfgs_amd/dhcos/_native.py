@@ -165,6 +165,10 @@ SIGNATURES = {
     "dh_surface_loss_grad": (_int, [_vp, _vp, _vp, _int, _dbl, _dbl, _int, _dbl, _vp, _vp, _vp]),
     "dh_surface_loss_grad_dev": (_int, [_vp, _vp, _vp, _int, _dbl, _dbl, _int, _dbl, _vp, _vp,
                                         _vp, _vp]),
+    "dh_surface_loss_grad_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int,
+                                         _dbl, _vp, _vp, _vp]),
+    "dh_surface_loss_grad_rows_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _dbl,
+                                             _vp, _vp, _vp, _vp]),
     # ---- Black-Scholes implied volatility
     "dh_implied_vol": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dh_implied_vol_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
@@ -187,6 +191,9 @@ SIGNATURES = {
                                        _vp, _vp, _vp]),
     "dh_calibrate_lbfgs_batch_iv": (_int, [_vp, _vp, _dp, _dp, _dp, _dp, _int, _dp, _i32p, _int,
                                            _int, _dbl, _lbo, _lbr, _i32p]),
+    # ---- many markets on one grid, with the analytic gradient
+    "dh_calibrate_lbfgs_batch_grad": (_int, [_vp, _vp, _dp, _dp, _dp, _int, _dp, _i32p, _int,
+                                             _int, _dbl, _lbo, _lbr, _i32p]),
     # ---- building blocks
     "dh_cf": (_int, [_vp, _dp, _dp, _int, _dbl, _dp, _dp]),
     "dh_cf_complex": (_int, [_vp, _dp, _dp, _dp, _int, _dbl, _dp, _dp]),
@@ -1139,6 +1146,50 @@ class Surface(_Handle):
         _check(load().dh_surface_loss_grad_dev(self.ctx.handle, self._h, _addr(d_x), int(S),
                                                float(S0), float(r), int(N), float(L), _addr(d_f),
                                                _addr(d_g), _addr(d_bad), _addr(stream)))
+
+    def loss_grad_rows(self, X, mkt, spots, rates, row, N=128, L=10.0):
+        """dh_surface_loss_grad_rows: loss_grad against a market row per set -- row s of X [S, 13]
+        under spots[row[s]] and rates[row[s]] against mkt[row[s]] of mkt [B, M] (the surface's
+        option order) -> (f [S], g [S, 13], bad [S]).  The surface needs no market prices."""
+        X = _f64(X).reshape(-1, 13)
+        S = X.shape[0]
+        mkt = self._market_rows(mkt)
+        B = mkt.shape[0]
+        spots, rates = _f64(spots).reshape(-1), _f64(rates).reshape(-1)
+        if spots.size != B or rates.size != B:
+            raise ValueError("mkt, spots and rates differ in length")
+        row = np.ascontiguousarray(row, dtype=np.int32).reshape(-1)
+        if row.size != S:
+            raise ValueError("X and row differ in length")
+        f, g, bad = np.empty(S), np.empty((S, 13)), np.empty(S, dtype=np.int32)
+        with self.ctx._lock:
+            _check(load().dh_surface_loss_grad_rows(
+                self.ctx.handle, self._h, _addr(X, S), _addr(mkt, B), _addr(spots, B),
+                _addr(rates, B), _addr(row, S), S, B, int(N), float(L), f.ctypes.data,
+                g.ctypes.data, bad.ctypes.data))
+        return f, g, bad
+
+    def loss_grad_rows_dev(self, d_x: int, d_mkt: int, d_spot: int, d_rate: int, d_row: int,
+                           S: int, d_f: int, d_g: int, d_bad: int, N=128, L=10.0,
+                           stream: int = 0):
+        """dh_surface_loss_grad_rows_dev: d_x [S, 13], d_mkt [B, M], d_spot [B], d_rate [B], d_row
+        [S] (int32) in, d_f [S], d_g [S, 13], d_bad [S] (int32) out, enqueued on stream."""
+        _check(load().dh_surface_loss_grad_rows_dev(
+            self.ctx.handle, self._h, _addr(d_x), _addr(d_mkt), _addr(d_spot), _addr(d_rate),
+            _addr(d_row), int(S), int(N), float(L), _addr(d_f), _addr(d_g), _addr(d_bad),
+            _addr(stream)))
+
+    def calibrate_lbfgs_batch_grad(self, mkt, spots, rates, x0s, market_of, N=128, L=10.0, *,
+                                   maxiter=300, maxfun=15000, maxls=20, ftol=1e-9, gtol=1e-6,
+                                   chunk=8, ctx=None):
+        """calibrate_lbfgs_batch with the analytic gradient (dh_calibrate_lbfgs_batch_grad): one
+        loss evaluation per request (n_calls == nfev), N <= PARAM_GRAD_MAX_N.
+        -> (list of LbResult, number of iterations enqueued)."""
+        mkt, spots, rates, x0s, mof = lb_batch_args(self.M, mkt, spots, rates, x0s, market_of)
+        B, S = mkt.shape[0], x0s.shape[0]
+        return _lbfgs("dh_calibrate_lbfgs_batch_grad", ctx or self.ctx, self, S,
+                      (_ptr(mkt), _ptr(spots), _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p), S,
+                       int(N), float(L)), maxiter, maxfun, maxls, chunk, ftol, gtol)
 
     def price_dev(self, d_params: int, P: int, d_out: int, N=128, L=10.0, stream: int = 0):
         _check(load().dh_surface_price_dev(self.ctx.handle, self._h, d_params, int(P), int(N),

@@ -12,6 +12,10 @@ market's result does not depend on what else is in the batch.
 ``objective="iv"`` fits implied vols instead of relative prices (dh_calibrate_lbfgs_batch_iv,
 DESIGN.md 3.13): the loss of a market is sum_m w_m (iv_model,m - iv_mkt,m)^2 / sum(w) + Feller,
 with every model price inverted on the device under its own market's spot and rate.
+
+``gradient="analytic"`` hands the optimiser the exact gradient of the price objective
+(dh_calibrate_lbfgs_batch_grad): a request is one point per start -- the parameter
+planes of its record and a reduction against its market's prices -- where ``"fd"`` prices fourteen.
 """
 from __future__ import annotations
 
@@ -27,6 +31,7 @@ from .generator import MATURITIES, STRIKES_PCT, grid_surface
 from .pricer import implied_vol, resolve_call
 
 OBJECTIVES = ("price", "iv")
+GRADIENTS = ("fd", "analytic")
 
 FAILED_MESSAGE = "All optimization starts failed"      # lbfgs_calibrator.py:318-333
 
@@ -85,6 +90,9 @@ class BatchCalibrationResult:
     market_ivs: np.ndarray = None    # [B, M] the vols fitted (None under "price")
     iv_weights: np.ndarray = None    # [B, M]
     model_ivs: np.ndarray = None     # [B, M] the winners' vols, NaN where a price has none
+    # "fd": 14 loss evaluations per request; "analytic": one (n_calls == nfev)
+    gradient: str = "fd"
+    loss_evals: int = 0              # loss evaluations of the whole call: n_calls summed
 
     def message(self, b: int) -> str:
         return task_message(self.task[b]) if self.best_start[b] >= 0 else FAILED_MESSAGE
@@ -158,6 +166,21 @@ def check_objective(objective):
     if objective not in OBJECTIVES:
         raise ValueError(f"objective must be 'price' or 'iv', not {objective!r}")
     return objective
+
+
+def check_gradient(gradient, objective, N):
+    """The gradient switch of calibrate_batch, or ValueError: "analytic" differentiates the price
+    objective only, on series of at most PARAM_GRAD_MAX_N terms."""
+    if gradient not in GRADIENTS:
+        raise ValueError(f"gradient must be 'fd' or 'analytic', not {gradient!r}")
+    if gradient == "analytic":
+        if objective != "price":
+            raise ValueError("gradient='analytic' differentiates the price objective only; "
+                             "objective='iv' runs gradient='fd'")
+        if not (isinstance(N, (int, np.integer)) and 1 <= N <= _native.PARAM_GRAD_MAX_N):
+            raise ValueError("gradient='analytic': N must be a whole number in "
+                             f"[1, {_native.PARAM_GRAD_MAX_N}], got {N!r}")
+    return gradient
 
 
 def check_iv_market(market_ivs, iv_weights, B, M):
@@ -251,7 +274,7 @@ def _surface(ctx, K, T, flags, mode, strikes_pct, maturities):
 
 def summarize(mkt, sp, r, Kabs, T, flags, X, fun, nit, nfev, task, status, best_loss, n_calls,
               t_done, model_prices_of, enqueued=0, *, objective="price", market_ivs=None,
-              iv_weights=None) -> BatchCalibrationResult:
+              iv_weights=None, gradient="fd") -> BatchCalibrationResult:
     """Per-market rows from per-start results [B, S]: the winner of each market
     (pick_winners), re-priced by model_prices_of(params [W, 13], markets [W]) -> [W, M] in one
     call; a market without a winner gets the reference's failure row (zeros, inf, success
@@ -289,13 +312,14 @@ def summarize(mkt, sp, r, Kabs, T, flags, X, fun, nit, nfev, task, status, best_
         best_start=best, model_prices=model, calibration_time=ctime, fun=fun, nit=nit, nfev=nfev,
         start_task=task, status=status, best_loss=best_loss, n_calls=n_calls, start_x=X,
         iterations_enqueued=enqueued, objective=objective, market_ivs=market_ivs,
-        iv_weights=iv_weights, model_ivs=model_iv)
+        iv_weights=iv_weights, model_ivs=model_iv, gradient=gradient,
+        loss_evals=int(np.sum(n_calls)))
 
 
 def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
                     maturities=MATURITIES, strikes=None, is_call=True, x0s=None, multi_start=3,
                     maxiter=300, N=128, device=None, chunk=8, objective="price",
-                    market_ivs=None, iv_weights=None) -> BatchCalibrationResult:
+                    market_ivs=None, iv_weights=None, gradient="fd") -> BatchCalibrationResult:
     """Calibrate B markets that share one option grid, all starts of all markets together in the
     device-resident L-BFGS-B.
 
@@ -318,8 +342,18 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
         calibrate_batch(g["market_prices"], g["spot"], g["risk_free"], objective="iv",
                         market_ivs=g["market_iv"], x0s=...)
 
-    One market in vol space on the device is this call with B = 1."""
+    One market in vol space on the device is this call with B = 1.
+
+    gradient="fd" (the default): SciPy's forward differences on the device, 14 loss evaluations
+    per request, the reference's optimiser.  gradient="analytic": the loss and its exact gradient
+    from one evaluation per request (dh_calibrate_lbfgs_batch_grad: the COS series differentiated
+    term by term at a fixed truncation range); the price objective only, N <= 1024.  The result's
+    n_calls and loss_evals then count one evaluation per request (n_calls == nfev).  On the Feller
+    kink the analytic gradient is the penalty's one-sided derivative, not the forward quotient's
+    slope, so a start on it may move where the "fd" run stalls.  One market with the analytic
+    gradient on the device is this call with B = 1 (calibrate(driver="device") runs "fd" only)."""
     check_objective(objective)
+    check_gradient(gradient, objective, N)
     if objective == "price" and (market_ivs is not None or iv_weights is not None):
         raise ValueError("market_ivs and iv_weights belong to objective='iv'")
     K, T, flags, mode = _grid(strikes_pct, maturities, strikes, is_call)
@@ -347,9 +381,10 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
                                                       market_of, N, maxiter=maxiter,
                                                       maxfun=_MAXFUN, chunk=chunk)
     else:
-        res, enqueued = surf.calibrate_lbfgs_batch(mkt, sp, r, X.reshape(B * S, N_PARAMS),
-                                                   market_of, N, maxiter=maxiter, maxfun=_MAXFUN,
-                                                   chunk=chunk)
+        run = (surf.calibrate_lbfgs_batch_grad if gradient == "analytic"
+               else surf.calibrate_lbfgs_batch)
+        res, enqueued = run(mkt, sp, r, X.reshape(B * S, N_PARAMS), market_of, N,
+                            maxiter=maxiter, maxfun=_MAXFUN, chunk=chunk)
 
     def col(name, dtype):
         return np.array([getattr(q, name) for q in res], dtype=dtype).reshape(B, S)
@@ -370,4 +405,5 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
                      col("nit", np.int64), col("nfev", np.int64), col("task", np.int64),
                      col("warnflag", np.int64), col("best_loss", np.float64),
                      col("n_calls", np.int64), col("t_done", np.float64), model_prices_of,
-                     enqueued, objective=objective, market_ivs=ivs, iv_weights=wts)
+                     enqueued, objective=objective, market_ivs=ivs, iv_weights=wts,
+                     gradient=gradient)

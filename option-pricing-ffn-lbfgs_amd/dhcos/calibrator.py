@@ -234,7 +234,8 @@ class DoubleHestonJumpCalibrator:
         and not with a subclass that replaces the loss.  The Feller penalty's derivative is taken
         where its slack is strictly positive, so on the kink itself (the literature start) the
         gradient differs from the forward quotient and that start may move where the "fd" run
-        stops at once."""
+        stops at once.  One market with the analytic gradient on the device is
+        dhcos.calibrate_batch(..., gradient="analytic") with B = 1."""
         if objective not in ("price", "iv"):
             raise ValueError(f"objective must be 'price' or 'iv', not {objective!r}")
         if gradient not in ("fd", "analytic"):
@@ -511,14 +512,17 @@ class DoubleHestonJumpCalibrator:
         GPU, the host checks for finished starts every few iterations); same algorithm and
         stopping rules, with the subspace step rounded differently (csrc/dh_lbfgs.h).
         driver="device" is refused with objective="iv": one market in vol space on the device
-        is ``dhcos.calibrate_batch(..., objective="iv")`` with B = 1."""
+        is ``dhcos.calibrate_batch(..., objective="iv")`` with B = 1.  It is refused with
+        gradient="analytic" as well: that is ``dhcos.calibrate_batch(..., gradient="analytic")``
+        with B = 1."""
         start_time = time.time()
         if driver == "device" and self.objective != "price":
             raise ValueError("driver='device' optimises the price objective only; "
                              "objective='iv' runs driver='scipy'")
         if driver == "device" and self.gradient != "fd":
             raise ValueError("driver='device' forms forward differences on the device; "
-                             "gradient='analytic' runs driver='scipy'")
+                             "gradient='analytic' runs driver='scipy', or on the device through "
+                             "calibrate_batch(gradient='analytic') with one market")
         # draw every start's x0 in start order (the only consumer of the global RNG, :256)
         if x0s is None:
             x0s = self.start_points(multi_start, x0)
@@ -1069,13 +1073,15 @@ def run_starts_device(cal: DoubleHestonJumpCalibrator, x0s, maxiter: int):
     nothing to optimise on the device and take the host driver, which reproduces the
     reference's result for them.  A calibrator with objective="iv" is refused: the vol-space
     objective runs on the device through ``dhcos.calibrate_batch(..., objective="iv")`` (one
-    market: B = 1)."""
+    market: B = 1).  So is one with gradient="analytic": that is
+    ``dhcos.calibrate_batch(..., gradient="analytic")``."""
     n = len(x0s)
     if getattr(cal, "objective", "price") != "price":
         raise ValueError("the device-resident L-BFGS-B optimises the price objective only")
     if getattr(cal, "gradient", "fd") != "fd":
         raise ValueError("the device-resident L-BFGS-B forms forward differences on the device; "
-                         "gradient='analytic' runs driver='scipy'")
+                         "gradient='analytic' runs driver='scipy', or on the device through "
+                         "calibrate_batch(gradient='analytic') with one market")
     if n == 0:
         return []
     surf = cal._get_surface()
