@@ -1,5 +1,5 @@
 """NumPy restatement of the analytic COS Greeks (include/dhcos.h) -- a helper of
-tests/test_greeks.py and tests/test_gpu_greeks.py, not a test.
+tests/test_greeks*.py and tests/test_gpu_greeks*.py, not a test.
 
 Built on oracle.dh_oracle (cf, _heston_factor, trunc_range) and written in price_vec's operation
 order, so that its price plane IS price_vec, bit for bit.  With xK = log(K / S0), [a, b] =
@@ -27,8 +27,19 @@ def clamp_active(prm, S0, K, T, r, L=10.0):
     return bool(a == x - 0.1 or b == x + 0.1)
 
 
-def greeks_vec(prm, S0, K, T, r, is_call, N=128, q=0.0, L=10.0):
-    """The six planes of one option as a dict of floats; 'price' equals O.price_vec bit for bit."""
+def unclamped_range(prm, T, r, L=10.0):
+    """The cumulant range (a0, b0) before the log-strike clamp, in trunc_range's arithmetic."""
+    v01, k1, t1, s1, r1, v02, k2, t2, s2, r2, lam, muj, sj = prm
+    c1a, c2a = O._factor_cumulants(T, r, v01, k1, t1, s1, r1)
+    c1b, c2b = O._factor_cumulants(T, r, v02, k2, t2, s2, r2)
+    c1 = c1a + c1b + lam * T * muj
+    c2 = c2a + c2b + lam * T * (sj ** 2 + muj ** 2)
+    half = L * np.sqrt(np.abs(c2))
+    return c1 - half, c1 + half
+
+
+def _plane_terms(prm, S0, K, T, r, is_call, N, q, L):
+    """(e^{-rT}, {plane: its N terms, halved at k = 0}) in price_vec's operation order."""
     v01, k1, t1, s1, r1, v02, k2, t2, s2, r2, lam, muj, sj = prm
     xK = np.log(K / S0)
     a, b = O.trunc_range(prm, S0, K, T, r, L)
@@ -57,14 +68,28 @@ def greeks_vec(prm, S0, K, T, r, is_call, N=128, q=0.0, L=10.0):
         w = phi * np.exp(-1j * u * a)
         disc = np.exp(-r * T)
 
-        def series(weights, coef):
-            terms = np.real(weights) * coef
-            terms[0] *= 0.5
-            return disc * np.sum(terms)
+        def terms(weights, coef):
+            t = np.real(weights) * coef
+            t[0] *= 0.5
+            return t
 
-        return {"price": series(w, V), "delta": series(w, Vd), "gamma": series(w, Vg),
-                "dual_delta": series(w, Vk), "vega1": series(w * B1, V),
-                "vega2": series(w * B2, V)}
+        return disc, {"price": terms(w, V), "delta": terms(w, Vd), "gamma": terms(w, Vg),
+                      "dual_delta": terms(w, Vk), "vega1": terms(w * B1, V),
+                      "vega2": terms(w * B2, V)}
+
+
+def greeks_vec(prm, S0, K, T, r, is_call, N=128, q=0.0, L=10.0):
+    """The six planes of one option as a dict of floats; 'price' equals O.price_vec bit for bit."""
+    disc, terms = _plane_terms(prm, S0, K, T, r, is_call, N, q, L)
+    with np.errstate(all="ignore"):
+        return {name: disc * np.sum(t) for name, t in terms.items()}
+
+
+def term_sums(prm, S0, K, T, r, is_call, N=128, q=0.0, L=10.0):
+    """e^{-rT} sum_k |term_k| per plane, in fp64: the series' absolute term sum, the unit in which
+    tests/test_greeks_truth.py and tests/test_gpu_greeks_truth.py state their bars."""
+    disc, terms = _plane_terms(prm, S0, K, T, r, is_call, N, q, L)
+    return {name: disc * np.sum(np.abs(t)) for name, t in terms.items()}
 
 
 def greeks_surface(records, K, T, is_call, N=128, L=10.0, pct_spot=False):
