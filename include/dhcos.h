@@ -643,6 +643,63 @@ int dh_calibrate_lbfgs_batch_grad(dh_ctx* ctx, const dh_surface* s, const double
                                   const int32_t* market_of, int S, int N, double L,
                                   const dh_lb_options* opt, dh_lb_result* out, int32_t* n_launches);
 
+/* ---- the vol objective with its exact gradient (csrc/dh_iv_grad.h) ------------- */
+/* The vol-space loss of dh_surface_loss_iv_rows and its exact gradient in the optimiser's x: the
+ * model vol v_m solves BS(v_m) = P_m, so dv_m/dtheta_i = (dP_m/dtheta_i) / vega_BS(v_m), with
+ * dP_m/dtheta_i the planes of dh_surface_param_sens and the vega closed-form in dh_implied_vol's
+ * variables (A = S0 e^{-qT}, B = K e^{-rT}, s = v sqrt T, h = |log1p((S0-K)/K) + (r-q)T| / s, t =
+ * s / 2: vega = sqrt A sqrt B sqrt T exp(-(h^2 + t^2)/2 - ln sqrt(2 pi))).
+ * The reduction stage alone, the vol-space sibling of dh_surface_iv_sse_rows_dev: d_planes
+ * [14][S][M] as dh_surface_param_sens_dev writes them (plane 0 the price; the caller's option
+ * order), d_params [S][16] the records they were formed under, d_pen [S] each record's Feller
+ * penalty, d_mkt_iv / d_wgt [B][M], d_row [S] (in [0, B); the caller's promise), d_div [S] the
+ * loss divisor of each set (its market's weight sum).  Per set s, by dh_surface_iv_sse_rows_dev's
+ * rules line for line (bad prices, the clamp at the lower bound, a zero weight enters nothing):
+ *   sse[s], n_bad[s], iv[s*M + m]: dh_surface_iv_sse_rows_dev's, bit for bit, for d_planes' plane
+ *                                  0 as its prices (d_sse, d_iv NULL to skip)
+ *   f[s]    = n_bad ? 1e10 : sse / div + pen
+ *   g[s][i] = n_bad ? 0 : (2 / div) sum_m c_m plane_i[m] dtheta_i/dx_i + dFeller/dx_i,
+ *             c_m = w_m (v_m - mkt_iv_m) / vega_m
+ * with dh_surface_loss_grad's transform and Feller expressions.  One-sided rule: an option whose
+ * vol as used is 0.0 (its price at, or a rounding below, its lower bound) or whose vega is not
+ * > 0 adds its residual to sse and nothing to g, as the Feller kink's flat side.  One wave per
+ * set: lane l takes the surface's sorted options l, l + 64, ... from 0.0, then the xor butterfly;
+ * nothing is contracted.  A set's outputs depend on nothing but its own record, planes, penalty
+ * and market row.  Enqueues on `stream` (NULL = the context's); no synchronisation; may grow the
+ * context's scratch by [S][M] doubles.                                                          */
+int dh_surface_iv_grad_rows_dev(dh_ctx* ctx, const dh_surface* s, const double* d_planes,
+                                const double* d_params, const double* d_pen,
+                                const double* d_mkt_iv, const double* d_wgt, const int32_t* d_row,
+                                const double* d_div, int S, double* d_f, double* d_g,
+                                double* d_sse, int32_t* d_n_bad, double* d_iv, void* stream);
+/* The request from x [S][13]: the records and penalties of dh_surface_loss_grad_rows_dev (set s
+ * under d_spot / d_rate [d_row[s]]), dh_surface_param_sens_dev's planes, the reduction above; d_f
+ * [S], d_g [S][13], d_bad [S] and the optional d_iv [S][M] out.  DH_E_ARG as
+ * dh_surface_loss_grad_rows_dev.                                                                */
+int dh_surface_loss_iv_grad_rows_dev(dh_ctx* ctx, const dh_surface* s, const double* d_x,
+                                     const double* d_mkt_iv, const double* d_wgt,
+                                     const double* d_div, const double* d_spot,
+                                     const double* d_rate, const int32_t* d_row, int S, int N,
+                                     double L, double* d_f, double* d_g, int32_t* d_bad,
+                                     double* d_iv, void* stream);
+/* The host-pointer form, synchronous: mkt_iv [B][M], wgt [B][M] (NULL: every weight 1), spot [B],
+ * rate [B], row [S]; each market's weight sum is formed as dh_calibrate_lbfgs_batch_iv forms it.
+ * DH_E_ARG as dh_surface_loss_grad_rows, and for that call's vol and weight cases.              */
+int dh_surface_loss_iv_grad_rows(dh_ctx* ctx, const dh_surface* s, const double* x,
+                                 const double* mkt_iv, const double* wgt, const double* spot,
+                                 const double* rate, const int32_t* row, int S, int B, int N,
+                                 double L, double* f, double* g, int32_t* bad, double* iv);
+/* dh_calibrate_lbfgs_batch_iv with that gradient where it forms SciPy's forward quotient: a
+ * request is ONE point per start, and every iteration is the parameter-plane launch, the
+ * reduction above and dh_calibrate_lbfgs_batch_grad's step launch, unchanged.  n_calls == nfev.
+ * The arguments and DH_E_ARG cases are dh_calibrate_lbfgs_batch_iv's, and
+ * dh_calibrate_lbfgs_batch_grad's for N and L; isolation, the trace and the scratch as there.  */
+int dh_calibrate_lbfgs_batch_iv_grad(dh_ctx* ctx, const dh_surface* s, const double* mkt_iv,
+                                     const double* wgt, const double* spot, const double* rate,
+                                     int B, const double* x0, const int32_t* market_of, int S,
+                                     int N, double L, const dh_lb_options* opt, dh_lb_result* out,
+                                     int32_t* n_launches);
+
 /* ---- building blocks (exposed for API parity with the reference's public methods) -------- */
 /* phi(u_j; tau) for one param set: DoubleHeston.characteristic_function (double_heston.py:48-97) */
 int dh_cf(dh_ctx* ctx, const double* params, const double* u, int n, double tau, double* re,

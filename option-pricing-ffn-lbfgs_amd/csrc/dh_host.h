@@ -161,8 +161,9 @@ struct dh_ctx {
     DevBuf rows_mkt, rows_row;         // market rows / row of each set (dh_loss_rows.h)
     // dh_calibrate_lbfgs_batch: the requests' prices, and each start's spot, rate and market
     DevBuf lb_prices, lb_spot, lb_rate, lb_mof;
-    // the vol-space rows (dh_loss_rows.h): weight rows [B][M], each start's weight sum
-    DevBuf rows_wgt, lb_div;
+    // the vol-space rows (dh_loss_rows.h): weight rows [B][M], each start's weight sum; each
+    // market's [B] (dh_calibrate_lbfgs_batch_iv_grad)
+    DevBuf rows_wgt, lb_div, lb_wsum;
     // the Monte Carlo pricer (dh_mc.h): staged records, sorted options / observation steps, the
     // blocks' partial sums (two per option, five under a control), staged outputs
     DevBuf mc_params, mc_opts, mc_part, mc_out;

@@ -2829,5 +2829,7 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
 #include "dh_greeks.h"       // analytic Greeks of the COS price: dh_host.h
 #include "dh_param_grad.h"   // analytic parameter sensitivities, loss + gradient: dh_greeks.h,
                              // dh_loss_rows.h, dh_api.h
-#include "dh_lb_driver.h"    // the device-resident L-BFGS-B: dh_api.h, dh_iv_loss.h, dh_loss_rows.h,
+#include "dh_iv_grad.h"      // the vol objective's exact gradient: dh_iv_loss.h, dh_loss_rows.h,
                              // dh_param_grad.h
+#include "dh_lb_driver.h"    // the device-resident L-BFGS-B: dh_api.h, dh_iv_loss.h, dh_loss_rows.h,
+                             // dh_param_grad.h, dh_iv_grad.h

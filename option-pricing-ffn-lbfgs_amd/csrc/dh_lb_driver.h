@@ -1,10 +1,10 @@
 // dh_lb_driver.h -- the device-resident multi-start L-BFGS-B driver (dh_calibrate_lbfgs,
 // dh_calibrate_lbfgs_batch, dh_calibrate_lbfgs_batch_iv, dh_calibrate_lbfgs_batch_grad,
-// dh_ctx_set_lb_trace, dh_ctx_read_lb_trace): the step kernel, its launch and the host loop.
-// Included by dh_kernels.hip after the loss stages (dh_iv_loss.h, dh_loss_rows.h,
-// dh_param_grad.h), whose launches the host loop calls; kInvalidLoss, kFdStep, kSqrtEps and
-// lb_transform, which the one-shot entry points share, stay in dh_kernels.hip.  DESIGN.md 3.8,
-// 3.12-3.14, 3.19.
+// dh_calibrate_lbfgs_batch_iv_grad, dh_ctx_set_lb_trace, dh_ctx_read_lb_trace): the step kernel,
+// its launch and the host loop.  Included by dh_kernels.hip after the loss stages (dh_iv_loss.h,
+// dh_loss_rows.h, dh_param_grad.h, dh_iv_grad.h), whose launches the host loop calls;
+// kInvalidLoss, kFdStep, kSqrtEps and lb_transform, which the one-shot entry points share, stay in
+// dh_kernels.hip.  DESIGN.md 3.8, 3.12-3.14, 3.19, 3.20.
 //
 // Nothing here is contracted into FMAs: the step kernel must compute the bits of the CPU build
 // of dh_lbfgs.h (tests/native/lb_host.cpp).
@@ -308,7 +308,8 @@ __device__ __forceinline__ void lb_tile_tree(const double* ps, int nt, double& s
 // the loss divides it by the start's weight sum (div_of) where the price objective divides by M.
 // kG (with kB): dh_calibrate_lbfgs_batch_grad's builds -- the request is one point, its loss (sse)
 // and gradient (grad) come finished from dh_param_grad.h's rows reduction, and the next request
-// is the one record of lb_emit_grad.
+// is the one record of lb_emit_grad.  dh_calibrate_lbfgs_batch_iv_grad runs the kG builds as they
+// are: dh_iv_grad.h's reduction hands them a finished f and g as dh_param_grad.h's does.
 template <bool kPre, bool kB = false, bool kIv = false, bool kG = false>
 __global__ __launch_bounds__(64) void lb_step_kernel(
     LbSlot* __restrict__ h_states, const double* __restrict__ h_part, int h_ntiles, int h_mode,
@@ -524,7 +525,8 @@ struct LbBatch {
     // market's weight sum [B] (null: the price objective)
     const double* iv_wgt = nullptr;
     const double* iv_wsum = nullptr;
-    // dh_calibrate_lbfgs_batch_grad: one analytic loss + gradient request per iteration
+    // dh_calibrate_lbfgs_batch_grad: one analytic loss + gradient request per iteration; with
+    // the weights, dh_calibrate_lbfgs_batch_iv_grad: the vol objective's (dh_iv_grad.h)
     bool grad = false;
 };
 
@@ -534,7 +536,8 @@ struct LbBatch {
 // dh_calibrate_lbfgs_batch (bt: a market per start, through price + dh_loss_rows.h's reduction)
 // and dh_calibrate_lbfgs_batch_iv (bt with weights: through price + dh_loss_rows.h's vol one)
 // and dh_calibrate_lbfgs_batch_grad (bt with grad: one record per start through dh_param_grad.h's
-// planes and rows reduction)
+// planes and rows reduction) and dh_calibrate_lbfgs_batch_iv_grad (bt with weights and grad: the
+// same planes through dh_iv_grad.h's reduction)
 static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, double S0, double r,
                   int N, double L, const dh_lb_options* opt, dh_lb_result* out,
                   int32_t* n_launches, const LbBatch* bt) {
@@ -598,7 +601,9 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
         HIP_TRY(ctx->rows_mkt.reserve(mb));
         HIP_TRY(ctx->rows_row.reserve(npts * 4));
         if (grad)   // once, for all S starts: the gradients [S][16], penalties [S], planes [14][S][M]
-            HIP_TRY(ctx->pg_scratch.reserve(dhpg::loss_grad_scratch(S, M)));
+                    // and under the vol objective the c_m plane [S][M] (dh_iv_grad.h)
+            HIP_TRY(ctx->pg_scratch.reserve(bt->iv_wgt ? dhivg::scratch_bytes(S, M)
+                                                       : dhpg::loss_grad_scratch(S, M)));
         else
             HIP_TRY(ctx->lb_prices.reserve(npts * M * 8));
         HIP_TRY(ctx->lb_spot.reserve((size_t)S * 8));
@@ -624,6 +629,14 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
             HIP_TRY(hipMemcpyAsync(ctx->rows_wgt.ptr, bt->iv_wgt, mb, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(ctx->lb_div.ptr, dv.data(), (size_t)S * 8,
                                    hipMemcpyHostToDevice, st));
+            if (grad) {
+                // dh_iv_grad.h's reduction works per slot, and a start changes slot at a
+                // compaction: it reads the divisor at the set's market row, so the sums go up
+                // per market as well
+                HIP_TRY(ctx->lb_wsum.reserve((size_t)bt->B * 8));
+                HIP_TRY(hipMemcpyAsync(ctx->lb_wsum.ptr, bt->iv_wsum, (size_t)bt->B * 8,
+                                       hipMemcpyHostToDevice, st));
+            }
         }
         HIP_TRY(hipStreamSynchronize(st));            // `sr`, `dv` are pageable and leave scope
     }
@@ -676,6 +689,7 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
     double* const d_grad = grad ? (double*)ctx->pg_scratch.ptr : nullptr;
     double* const d_pen = grad ? d_grad + (size_t)S * DH_PARAM_STRIDE : nullptr;
     double* const d_planes = grad ? d_pen + S : nullptr;
+    double* const d_cm = grad && iv ? d_planes + (size_t)dhpg::kPlanes * S * M : nullptr;
     A.grad = d_grad;
     A.pen_out = d_pen;
     auto set_inline = [&](const int* lst, int n) {
@@ -704,10 +718,17 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
             if (grad) {
                 // the planes of the live starts' records, then each set's loss and gradient
                 // against its start's market row; the step reads them finished
-                e = dhpg::loss_grad_rows_launch(ctx, s, A.rec, d_pen,
-                                                (const double*)ctx->rows_mkt.ptr, A.row, n_live, N,
-                                                L, d_planes, (double*)A.sse, d_grad, (int*)A.bad,
-                                                st, A.live_count);
+                if (iv)                                // rows_mkt holds vols
+                    e = dhivg::loss_iv_grad_rows_launch(
+                        ctx, s, A.rec, d_pen, (const double*)ctx->rows_mkt.ptr,
+                        (const double*)ctx->rows_wgt.ptr, A.row, (const double*)ctx->lb_wsum.ptr,
+                        true, n_live, N, L, d_planes, d_cm, (double*)A.sse, d_grad, (int*)A.bad,
+                        nullptr, st, A.live_count);
+                else
+                    e = dhpg::loss_grad_rows_launch(ctx, s, A.rec, d_pen,
+                                                    (const double*)ctx->rows_mkt.ptr, A.row,
+                                                    n_live, N, L, d_planes, (double*)A.sse, d_grad,
+                                                    (int*)A.bad, st, A.live_count);
                 if (e) return e;
                 e = launch_lb_step(st, A, n_live, true, false, true);
                 if (e) return e;
@@ -862,6 +883,27 @@ extern "C" int dh_calibrate_lbfgs_batch_grad(dh_ctx* ctx, const dh_surface* s, c
                                              int N, double L, const dh_lb_options* opt,
                                              dh_lb_result* out, int32_t* n_launches) {
     LbBatch bt{mkt, spot, rate, B, market_of};
+    bt.grad = true;
+    return lb_run(ctx, s, x0, S, 0.0, 0.0, N, L, opt, out, n_launches, &bt);
+}
+
+// The vol objective with its exact gradient: dh_calibrate_lbfgs_batch_iv's arguments and checks,
+// dh_calibrate_lbfgs_batch_grad's iteration with dh_iv_grad.h's reduction in place of the price
+// one.  The step kernel's kG builds run unchanged.
+extern "C" int dh_calibrate_lbfgs_batch_iv_grad(dh_ctx* ctx, const dh_surface* s,
+                                                const double* mkt_iv, const double* wgt,
+                                                const double* spot, const double* rate, int B,
+                                                const double* x0, const int32_t* market_of, int S,
+                                                int N, double L, const dh_lb_options* opt,
+                                                dh_lb_result* out, int32_t* n_launches) {
+    if (!ctx || !s || !opt || (S > 0 && (!x0 || !out)) || (B > 0 && !mkt_iv))
+        return fail(DH_E_ARG, "null argument");
+    std::vector<double> w((size_t)std::max(B, 0) * s->M), wsum((size_t)std::max(B, 0), 0.0);
+    const int rc = iv_check_weights(mkt_iv, wgt, B, s->M, true, w.data(), wsum.data());
+    if (rc) return rc;
+    LbBatch bt{mkt_iv, spot, rate, B, market_of};
+    bt.iv_wgt = w.data();
+    bt.iv_wsum = wsum.data();
     bt.grad = true;
     return lb_run(ctx, s, x0, S, 0.0, 0.0, N, L, opt, out, n_launches, &bt);
 }

@@ -194,6 +194,15 @@ SIGNATURES = {
     # ---- many markets on one grid, with the analytic gradient
     "dh_calibrate_lbfgs_batch_grad": (_int, [_vp, _vp, _dp, _dp, _dp, _int, _dp, _i32p, _int,
                                              _int, _dbl, _lbo, _lbr, _i32p]),
+    # ---- the vol objective with its exact gradient
+    "dh_surface_iv_grad_rows_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp,
+                                           _vp, _vp, _vp, _vp, _vp]),
+    "dh_surface_loss_iv_grad_rows_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int,
+                                                _int, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "dh_surface_loss_iv_grad_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int,
+                                            _int, _dbl, _vp, _vp, _vp, _vp]),
+    "dh_calibrate_lbfgs_batch_iv_grad": (_int, [_vp, _vp, _dp, _dp, _dp, _dp, _int, _dp, _i32p,
+                                                _int, _int, _dbl, _lbo, _lbr, _i32p]),
     # ---- building blocks
     "dh_cf": (_int, [_vp, _dp, _dp, _int, _dbl, _dp, _dp]),
     "dh_cf_complex": (_int, [_vp, _dp, _dp, _dp, _int, _dbl, _dp, _dp]),
@@ -1190,6 +1199,74 @@ class Surface(_Handle):
         return _lbfgs("dh_calibrate_lbfgs_batch_grad", ctx or self.ctx, self, S,
                       (_ptr(mkt), _ptr(spots), _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p), S,
                        int(N), float(L)), maxiter, maxfun, maxls, chunk, ftol, gtol)
+
+    def iv_grad_rows_dev(self, d_planes: int, d_params: int, d_pen: int, d_mkt_iv: int, d_wgt: int,
+                         d_row: int, d_div: int, S: int, d_f: int, d_g: int, d_bad: int,
+                         d_sse: int = 0, d_iv: int = 0, stream: int = 0):
+        """dh_surface_iv_grad_rows_dev: the vol objective's loss-and-gradient reduction alone over
+        d_planes [14, S, M] (param_sens_dev's), d_params [S, 16], d_pen [S], d_mkt_iv / d_wgt
+        [B, M], d_row [S] (int32), d_div [S] in; d_f [S], d_g [S, 13], d_bad [S] (int32) and the
+        optional d_sse [S], d_iv [S, M] out, enqueued on stream."""
+        _check(load().dh_surface_iv_grad_rows_dev(
+            self.ctx.handle, self._h, _addr(d_planes), _addr(d_params), _addr(d_pen),
+            _addr(d_mkt_iv), _addr(d_wgt), _addr(d_row), _addr(d_div), int(S), _addr(d_f),
+            _addr(d_g), _addr(d_sse), _addr(d_bad), _addr(d_iv), _addr(stream)))
+
+    def loss_iv_grad_rows(self, X, mkt_iv, wgt, spots, rates, row, N=128, L=10.0):
+        """dh_surface_loss_iv_grad_rows: the vol objective and its exact gradient (price
+        sensitivities over each option's Black-Scholes vega) against a market row per set -- row s
+        of X [S, 13] under spots[row[s]] and rates[row[s]] against the vols mkt_iv[row[s]] under
+        wgt[row[s]] (mkt_iv [B, M]; wgt [B, M] or None for all 1)
+        -> (f [S], g [S, 13], bad [S], iv [S, M] the vols as used)."""
+        X = _f64(X).reshape(-1, 13)
+        S = X.shape[0]
+        mkt_iv = self._market_rows(mkt_iv)
+        B = mkt_iv.shape[0]
+        w = None
+        if wgt is not None:
+            w = _f64(wgt)
+            if w.shape != mkt_iv.shape:
+                raise ValueError(f"wgt must be {mkt_iv.shape}, got {w.shape}")
+        spots, rates = _f64(spots).reshape(-1), _f64(rates).reshape(-1)
+        if spots.size != B or rates.size != B:
+            raise ValueError("mkt_iv, spots and rates differ in length")
+        row = np.ascontiguousarray(row, dtype=np.int32).reshape(-1)
+        if row.size != S:
+            raise ValueError("X and row differ in length")
+        f, g, bad = np.empty(S), np.empty((S, 13)), np.empty(S, dtype=np.int32)
+        iv = np.empty((S, self.M))
+        with self.ctx._lock:
+            _check(load().dh_surface_loss_iv_grad_rows(
+                self.ctx.handle, self._h, _addr(X, S), _addr(mkt_iv, B), _addr(w),
+                _addr(spots, B), _addr(rates, B), _addr(row, S), S, B, int(N), float(L),
+                f.ctypes.data, g.ctypes.data, bad.ctypes.data, iv.ctypes.data))
+        return f, g, bad, iv
+
+    def loss_iv_grad_rows_dev(self, d_x: int, d_mkt_iv: int, d_wgt: int, d_div: int, d_spot: int,
+                              d_rate: int, d_row: int, S: int, d_f: int, d_g: int, d_bad: int,
+                              d_iv: int = 0, N=128, L=10.0, stream: int = 0):
+        """dh_surface_loss_iv_grad_rows_dev: d_x [S, 13], d_mkt_iv / d_wgt [B, M], d_div [S], d_spot
+        [B], d_rate [B], d_row [S] (int32) in, d_f [S], d_g [S, 13], d_bad [S] (int32) and the
+        optional d_iv [S, M] out, enqueued on stream."""
+        _check(load().dh_surface_loss_iv_grad_rows_dev(
+            self.ctx.handle, self._h, _addr(d_x), _addr(d_mkt_iv), _addr(d_wgt), _addr(d_div),
+            _addr(d_spot), _addr(d_rate), _addr(d_row), int(S), int(N), float(L), _addr(d_f),
+            _addr(d_g), _addr(d_bad), _addr(d_iv), _addr(stream)))
+
+    def calibrate_lbfgs_batch_iv_grad(self, mkt_iv, weights, spots, rates, x0s, market_of, N=128,
+                                      L=10.0, *, maxiter=300, maxfun=15000, maxls=20, ftol=1e-9,
+                                      gtol=1e-6, chunk=8, ctx=None):
+        """calibrate_lbfgs_batch_iv with the vol objective's exact gradient
+        (dh_calibrate_lbfgs_batch_iv_grad): one loss evaluation per request (n_calls == nfev), N <=
+        PARAM_GRAD_MAX_N.  -> (list of LbResult, number of iterations enqueued)."""
+        mkt_iv, spots, rates, x0s, mof = lb_batch_args(self.M, mkt_iv, spots, rates, x0s,
+                                                       market_of)
+        mkt_iv, w = iv_rows(self.M, mkt_iv, weights)
+        B, S = mkt_iv.shape[0], x0s.shape[0]
+        return _lbfgs("dh_calibrate_lbfgs_batch_iv_grad", ctx or self.ctx, self, S,
+                      (_ptr(mkt_iv), _ptr(w), _ptr(spots), _ptr(rates), B, _ptr(x0s),
+                       _ptr(mof, _i32p), S, int(N), float(L)),
+                      maxiter, maxfun, maxls, chunk, ftol, gtol)
 
     def price_dev(self, d_params: int, P: int, d_out: int, N=128, L=10.0, stream: int = 0):
         _check(load().dh_surface_price_dev(self.ctx.handle, self._h, d_params, int(P), int(N),

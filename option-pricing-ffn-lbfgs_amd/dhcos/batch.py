@@ -16,6 +16,11 @@ with every model price inverted on the device under its own market's spot and ra
 ``gradient="analytic"`` hands the optimiser the exact gradient of the price objective
 (dh_calibrate_lbfgs_batch_grad): a request is one point per start -- the parameter
 planes of its record and a reduction against its market's prices -- where ``"fd"`` prices fourteen.
+
+``objective="iv"`` with ``gradient="vega"`` is the vol objective's exact gradient
+(dh_calibrate_lbfgs_batch_iv_grad): the same parameter planes, each option's price
+sensitivities divided by its Black-Scholes vega.  A request inverts M prices where ``"fd"`` inverts
+14 M, and no inverter noise is divided by the difference step.
 """
 from __future__ import annotations
 
@@ -32,6 +37,7 @@ from .pricer import implied_vol, resolve_call
 
 OBJECTIVES = ("price", "iv")
 GRADIENTS = ("fd", "analytic")
+IV_GRADIENTS = ("fd", "vega")                          # objective="iv"'s
 
 FAILED_MESSAGE = "All optimization starts failed"      # lbfgs_calibrator.py:318-333
 
@@ -90,7 +96,7 @@ class BatchCalibrationResult:
     market_ivs: np.ndarray = None    # [B, M] the vols fitted (None under "price")
     iv_weights: np.ndarray = None    # [B, M]
     model_ivs: np.ndarray = None     # [B, M] the winners' vols, NaN where a price has none
-    # "fd": 14 loss evaluations per request; "analytic": one (n_calls == nfev)
+    # "fd": 14 loss evaluations per request; "analytic" and "vega": one (n_calls == nfev)
     gradient: str = "fd"
     loss_evals: int = 0              # loss evaluations of the whole call: n_calls summed
 
@@ -170,15 +176,20 @@ def check_objective(objective):
 
 def check_gradient(gradient, objective, N):
     """The gradient switch of calibrate_batch, or ValueError: "analytic" differentiates the price
-    objective only, on series of at most PARAM_GRAD_MAX_N terms."""
-    if gradient not in GRADIENTS:
-        raise ValueError(f"gradient must be 'fd' or 'analytic', not {gradient!r}")
-    if gradient == "analytic":
-        if objective != "price":
-            raise ValueError("gradient='analytic' differentiates the price objective only; "
-                             "objective='iv' runs gradient='fd'")
+    objective only and "vega" the vol objective only, both on series of at most PARAM_GRAD_MAX_N
+    terms."""
+    if gradient not in GRADIENTS and gradient not in IV_GRADIENTS:
+        raise ValueError(f"gradient must be 'fd', 'analytic' or 'vega', not {gradient!r}")
+    if gradient == "analytic" and objective != "price":
+        raise ValueError("gradient='analytic' differentiates the price objective only; "
+                         "objective='iv' runs gradient='fd' or its exact gradient, "
+                         "gradient='vega'")
+    if gradient == "vega" and objective != "iv":
+        raise ValueError("gradient='vega' differentiates the vol objective (objective='iv') only; "
+                         "objective='price' runs gradient='fd' or gradient='analytic'")
+    if gradient != "fd":
         if not (isinstance(N, (int, np.integer)) and 1 <= N <= _native.PARAM_GRAD_MAX_N):
-            raise ValueError("gradient='analytic': N must be a whole number in "
+            raise ValueError(f"gradient={gradient!r}: N must be a whole number in "
                              f"[1, {_native.PARAM_GRAD_MAX_N}], got {N!r}")
     return gradient
 
@@ -351,7 +362,12 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
     n_calls and loss_evals then count one evaluation per request (n_calls == nfev).  On the Feller
     kink the analytic gradient is the penalty's one-sided derivative, not the forward quotient's
     slope, so a start on it may move where the "fd" run stalls.  One market with the analytic
-    gradient on the device is this call with B = 1 (calibrate(driver="device") runs "fd" only)."""
+    gradient on the device is this call with B = 1 (calibrate(driver="device") runs "fd" only).
+    gradient="vega": the same for objective="iv", and for it only
+    (dh_calibrate_lbfgs_batch_iv_grad: each option's price sensitivities divided by its
+    Black-Scholes vega at the model vol); N <= 1024, n_calls == nfev.  An option whose model price
+    sits at its lower bound (vol 0.0) adds its residual to the loss and nothing to the gradient,
+    the one-sided rule of the Feller kink."""
     check_objective(objective)
     check_gradient(gradient, objective, N)
     if objective == "price" and (market_ivs is not None or iv_weights is not None):
@@ -377,9 +393,10 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
     surf = _surface(ctx, K, T, flags, mode, strikes_pct, maturities)
     market_of = np.repeat(np.arange(B, dtype=np.int32), S)
     if objective == "iv":
-        res, enqueued = surf.calibrate_lbfgs_batch_iv(ivs, wts, sp, r, X.reshape(B * S, N_PARAMS),
-                                                      market_of, N, maxiter=maxiter,
-                                                      maxfun=_MAXFUN, chunk=chunk)
+        run = (surf.calibrate_lbfgs_batch_iv_grad if gradient == "vega"
+               else surf.calibrate_lbfgs_batch_iv)
+        res, enqueued = run(ivs, wts, sp, r, X.reshape(B * S, N_PARAMS), market_of, N,
+                            maxiter=maxiter, maxfun=_MAXFUN, chunk=chunk)
     else:
         run = (surf.calibrate_lbfgs_batch_grad if gradient == "analytic"
                else surf.calibrate_lbfgs_batch)

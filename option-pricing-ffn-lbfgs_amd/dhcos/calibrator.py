@@ -235,20 +235,27 @@ class DoubleHestonJumpCalibrator:
         where its slack is strictly positive, so on the kink itself (the literature start) the
         gradient differs from the forward quotient and that start may move where the "fd" run
         stops at once.  One market with the analytic gradient on the device is
-        dhcos.calibrate_batch(..., gradient="analytic") with B = 1."""
+        dhcos.calibrate_batch(..., gradient="analytic") with B = 1.
+        gradient="vega": the same for objective="iv", and for it only -- the vol objective's exact
+        gradient, each option's price sensitivities divided by its Black-Scholes vega at the model
+        vol (dh_surface_loss_iv_grad_rows with this market as its one row)."""
         if objective not in ("price", "iv"):
             raise ValueError(f"objective must be 'price' or 'iv', not {objective!r}")
-        if gradient not in ("fd", "analytic"):
-            raise ValueError(f"gradient must be 'fd' or 'analytic', not {gradient!r}")
-        if gradient == "analytic":
-            if objective != "price":
-                raise ValueError("gradient='analytic' differentiates the price objective only; "
-                                 "objective='iv' runs gradient='fd'")
+        if gradient not in ("fd", "analytic", "vega"):
+            raise ValueError(f"gradient must be 'fd', 'analytic' or 'vega', not {gradient!r}")
+        if gradient == "analytic" and objective != "price":
+            raise ValueError("gradient='analytic' differentiates the price objective only; "
+                             "objective='iv' runs gradient='fd' or its exact gradient, "
+                             "gradient='vega'")
+        if gradient == "vega" and objective != "iv":
+            raise ValueError("gradient='vega' differentiates the vol objective (objective='iv') "
+                             "only; objective='price' runs gradient='fd' or gradient='analytic'")
+        if gradient != "fd":
             if _custom_loss(self):
-                raise ValueError("gradient='analytic' needs the built-in loss: this subclass "
+                raise ValueError(f"gradient={gradient!r} needs the built-in loss: this subclass "
                                  "replaces compute_loss or loss_batch (use gradient='fd')")
             if int(N) != N or not 1 <= N <= _native.PARAM_GRAD_MAX_N:
-                raise ValueError("gradient='analytic': N must be a whole number in "
+                raise ValueError(f"gradient={gradient!r}: N must be a whole number in "
                                  f"[1, {_native.PARAM_GRAD_MAX_N}], got {N!r}")
         self.objective = objective
         self.gradient = gradient
@@ -400,7 +407,7 @@ class DoubleHestonJumpCalibrator:
         request; the transforms by NumPy, fd_models) unless a subclass replaces loss_batch,
         whose values are then used the same way."""
         X0 = np.atleast_2d(np.asarray(X0, dtype=np.float64))
-        if self.gradient == "analytic":
+        if self.gradient in ("analytic", "vega"):
             return self._fg_analytic(X0)
         if self.objective == "iv":      # one request of the 14 S points, the difference on the host
             return fg_from_losses(self, X0)
@@ -415,14 +422,22 @@ class DoubleHestonJumpCalibrator:
         """fg_batch under gradient="analytic": (f, g, low) of dh_surface_loss_grad, one loss
         evaluation per row; low = f where the set is valid, inf where it is not (as the FD
         request's smallest valid loss).  No market: NaN (np.mean([])); an option type the reference
-        cannot read: 1e10; the gradient zero in both."""
+        cannot read: 1e10; the gradient zero in both.  gradient="vega": the same of
+        dh_surface_loss_iv_grad_rows, with the calibrator's own vols and weights as its one market
+        row."""
         S = X0.shape[0]
         self.loss_evals += S
         surf = self._get_surface() if len(self.market_options) else None
         if surf is None:
             f = np.full(S, INVALID_LOSS if len(self.market_options) else np.nan)
             return f, np.zeros((S, N_PARAMS)), np.full(S, np.inf)
-        f, g, bad = surf.loss_grad(X0, self.spot, self.risk_free_rate, self.N)
+        if self.gradient == "vega":
+            f, g, bad, _ = surf.loss_iv_grad_rows(X0, self.market_ivs[None, :],
+                                                  self.iv_weights[None, :], [self.spot],
+                                                  [self.risk_free_rate], np.zeros(S, np.int32),
+                                                  self.N)
+        else:
+            f, g, bad = surf.loss_grad(X0, self.spot, self.risk_free_rate, self.N)
         return f, g, np.where((bad > 0) | np.isnan(f), np.inf, f)
 
     def compute_loss(self, x: np.ndarray) -> float:
@@ -432,8 +447,8 @@ class DoubleHestonJumpCalibrator:
     def compute_loss_and_grad(self, x: np.ndarray, eps: float = FD_ABS_STEP):
         """(f, g) exactly as SciPy's 2-point forward difference would form them, from one launch
         of the 14 points (x and x + h e_i); under gradient="analytic" the loss and its exact
-        gradient from one evaluation (eps is not used)."""
-        if self.gradient == "analytic":
+        gradient from one evaluation (eps is not used); under gradient="vega" the vol objective's."""
+        if self.gradient in ("analytic", "vega"):
             f, g, low = self._fg_analytic(np.asarray(x, dtype=np.float64)[None, :N_PARAMS])
             self.n_calls += 1
             if low[0] < self.best_loss:
@@ -836,7 +851,7 @@ def _advance(cal, gens, states, order, outcomes):
     else through cal.fg_batch; both give the same values (fg_batch is dh_surface_fg)."""
     launches = 0
     # loss evaluations per request and start: the 14 FD points, or the analytic gradient's one
-    calls = 1 if getattr(cal, "gradient", "fd") == "analytic" else N_PARAMS + 1
+    calls = 1 if getattr(cal, "gradient", "fd") in ("analytic", "vega") else N_PARAMS + 1
     surf = _native_surface(cal, max(len(g) for g in order)) if order else None
     chan = None if surf is None else _native.FgChannel(surf, 0, max(len(g) for g in order),
                                                        cal.spot, cal.risk_free_rate, cal.N)
