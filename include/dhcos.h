@@ -700,6 +700,53 @@ int dh_calibrate_lbfgs_batch_iv_grad(dh_ctx* ctx, const dh_surface* s, const dou
                                      int N, double L, const dh_lb_options* opt, dh_lb_result* out,
                                      int32_t* n_launches);
 
+/* ---- Gauss-Newton Hessian and Levenberg-Marquardt (csrc/dh_gauss_newton.h, csrc/dh_lm.h,
+ *      DESIGN.md 3.21) -------------------------------------------------------------------------- */
+/* dh_surface_loss_grad_rows with the Gauss-Newton Hessian of the price part of the loss in the
+ * optimiser's x: the same arguments, stages, f [S], g [S][13] and bad [S] -- bit for bit -- and
+ *   H[s][i][j] = (2 / M) dt_i dt_j sum_m a_im a_jm,   a_im = plane_i[m] / mkt[row[s]][m]
+ * with plane_i dh_surface_param_sens's plane of parameter i and dt_i the transform's derivative
+ * dtheta_i/dx_i that g uses (1 - rho^2 for the two correlations, 1 for mu_j, the parameter itself
+ * otherwise), formed as ((2 / M) dt_i) dt_j times the sum.  The Feller penalty, piecewise linear in
+ * its slack, enters g only.  Every sum runs in dh_surface_loss_grad_rows's order (lane l adds the
+ * sorted options l, l + 64, ... from 0.0, then the xor butterfly); the 91 entries i <= j are
+ * computed and mirrored, so H is exactly symmetric; a set's bits depend on nothing but its own x
+ * and market row.  An invalid set (bad > 0) has f = 1e10, g = 0 and H = 0; a NaN market price gives
+ * NaN.  Host arrays, synchronous.  DH_E_ARG as dh_surface_loss_grad_rows, and for a NULL H.      */
+int dh_surface_gauss_newton_rows(dh_ctx* ctx, const dh_surface* s, const double* x,
+                                 const double* mkt, const double* spot, const double* rate,
+                                 const int32_t* row, int S, int B, int N, double L, double* f,
+                                 double* g, int32_t* bad, double* H);
+/* The same over device pointers, enqueued on `stream`; the same bits.  d_H [S][13][13]; the other
+ * arguments, the caller's promises, the scratch and the one request in flight per context are
+ * dh_surface_loss_grad_rows_dev's.                                                              */
+int dh_surface_gauss_newton_rows_dev(dh_ctx* ctx, const dh_surface* s, const double* d_x,
+                                     const double* d_mkt, const double* d_spot,
+                                     const double* d_rate, const int32_t* d_row, int S, int N,
+                                     double L, double* d_f, double* d_g, int32_t* d_bad,
+                                     double* d_H, void* stream);
+/* dh_lb_result.task of a dh_calibrate_lm_batch start: the two gradient and loss tolerances of
+ * dh_lb_options, the step tolerance, the two budgets, a damping past its ceiling (or a NaN gradient),
+ * and an invalid or NaN loss at x0.  warnflag is 0 for the first three, 1 for the budgets, 2 else. */
+enum { DH_LM_GTOL = 1, DH_LM_FTOL = 2, DH_LM_XTOL = 3, DH_LM_MAXITER = 4, DH_LM_MAXFUN = 5, DH_LM_STALLED = 6, DH_LM_INVALID_X0 = 7 };
+/* dh_calibrate_lbfgs_batch_grad's markets, starts, options and results under Levenberg-Marquardt
+ * on that Hessian (Nielsen's damping with Marquardt scaling; csrc/dh_lm.h states the algorithm and
+ * its constants).  Every iteration is the parameter-plane launch over one record per live start,
+ * the reduction above into f, g and H, and one step launch that accepts or rejects each start's
+ * trial point, solves (H + lambda diag(D)) delta = -g by Cholesky and writes the record of x +
+ * delta with the start's spot, rate, market row and Feller penalty.  One iteration is one request:
+ * nfev == n_calls counts requests (x0 included), nit accepted steps (opt->maxiter bounds nit,
+ * opt->maxfun nfev; opt->gtol and opt->ftol are the gradient and loss tolerances; maxls is checked
+ * and not used).  x is the last accepted point and fun its loss, so fun <= f(x0) and best_loss ==
+ * fun whenever f(x0) is valid; a start whose f(x0) is 1e10 or NaN ends at once with x = x0.  task
+ * is a DH_LM_* code.  The chunked enqueue, compaction and trace are dh_calibrate_lbfgs_batch's; a
+ * start's requests and results depend on nothing but its own x0 and market.  DH_E_ARG as
+ * dh_calibrate_lbfgs_batch_grad.                                                                */
+int dh_calibrate_lm_batch(dh_ctx* ctx, const dh_surface* s, const double* mkt, const double* spot,
+                          const double* rate, int B, const double* x0, const int32_t* market_of,
+                          int S, int N, double L, const dh_lb_options* opt, dh_lb_result* out,
+                          int32_t* n_launches);
+
 /* ---- building blocks (exposed for API parity with the reference's public methods) -------- */
 /* phi(u_j; tau) for one param set: DoubleHeston.characteristic_function (double_heston.py:48-97) */
 int dh_cf(dh_ctx* ctx, const double* params, const double* u, int n, double tau, double* re,

@@ -51,6 +51,7 @@
 #include "dh_device.h"
 #include "dh_index.h"
 #include "dh_lbfgs.h"
+#include "dh_lm.h"
 #include "dhcos.h"
 
 using dh::cplx;
@@ -2831,5 +2832,7 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
                              // dh_loss_rows.h, dh_api.h
 #include "dh_iv_grad.h"      // the vol objective's exact gradient: dh_iv_loss.h, dh_loss_rows.h,
                              // dh_param_grad.h
-#include "dh_lb_driver.h"    // the device-resident L-BFGS-B: dh_api.h, dh_iv_loss.h, dh_loss_rows.h,
-                             // dh_param_grad.h, dh_iv_grad.h
+#include "dh_gauss_newton.h" // the Gauss-Newton rows reduction: dh_param_grad.h, dh_loss_rows.h
+#include "dh_lb_driver.h"    // the device-resident L-BFGS-B and Levenberg-Marquardt: dh_api.h,
+                             // dh_iv_loss.h, dh_loss_rows.h, dh_param_grad.h, dh_iv_grad.h,
+                             // dh_gauss_newton.h

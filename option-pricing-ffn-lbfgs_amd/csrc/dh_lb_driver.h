@@ -1,7 +1,8 @@
 // dh_lb_driver.h -- the device-resident multi-start L-BFGS-B driver (dh_calibrate_lbfgs,
 // dh_calibrate_lbfgs_batch, dh_calibrate_lbfgs_batch_iv, dh_calibrate_lbfgs_batch_grad,
 // dh_calibrate_lbfgs_batch_iv_grad, dh_ctx_set_lb_trace, dh_ctx_read_lb_trace): the step kernel,
-// its launch and the host loop.  Included by dh_kernels.hip after the loss stages (dh_iv_loss.h,
+// its launch and the host loop; and the Levenberg-Marquardt driver on the same host loop
+// (dh_calibrate_lm_batch: lm_step_kernel around dh_lm.h's state machine).  Included by dh_kernels.hip after the loss stages (dh_iv_loss.h,
 // dh_loss_rows.h, dh_param_grad.h, dh_iv_grad.h), whose launches the host loop calls;
 // kInvalidLoss, kFdStep, kSqrtEps and lb_transform, which the one-shot entry points share, stay in
 // dh_kernels.hip.  DESIGN.md 3.8, 3.12-3.14, 3.19, 3.20.
@@ -238,14 +239,14 @@ __device__ void lb_emit(const WaveCore& c, WaveVec& dx, WaveVec& pen, double* pb
     }
 }
 
-// The analytic-gradient driver's request (dh_calibrate_lbfgs_batch_grad): the one record of xe, no
-// bumps and no dx.  Lane i < 13 maps x_i to its model param and writes it; lanes 13..15 write the
+// The analytic-gradient driver's request (dh_calibrate_lbfgs_batch_grad, and dh_calibrate_lm_batch's):
+// the one record of xe, no bumps and no dx.  Lane i < 13 maps x_i = xi to its model param and writes it; lanes 13..15 write the
 // start's spot, its rate and q = 0; lane 0 writes the set's market row and the record's Feller
 // penalty, x_records_kernel's expression, which the rows reduction adds to the loss.
-__device__ void lb_emit_grad(const WaveCore& c, WaveVec& dx, WaveVec& pen, double* pb,
-                             const LbArgs& A, int slot, int lane, int sidx) {
+__device__ void lb_emit_grad(double xi, WaveVec& dx, WaveVec& pen, double* pb, const LbArgs& A,
+                             int slot, int lane, int sidx) {
     dx.v = 0.0;
-    if (lane < dhlb::kN) pb[lane] = lb_transform(lane, c.xe.v);
+    if (lane < dhlb::kN) pb[lane] = lb_transform(lane, xi);
     __syncthreads();
     const double v1 = pb[3] * pb[3] - 2.0 * pb[1] * pb[2];
     const double v2 = pb[8] * pb[8] - 2.0 * pb[6] * pb[7];
@@ -454,7 +455,7 @@ __global__ __launch_bounds__(64) void lb_step_kernel(
         }
     }
     if constexpr (kG) {
-        if (need) lb_emit_grad(c, dx, pen, pb, A, slot, lane, sidx);
+        if (need) lb_emit_grad(c.xe.v, dx, pen, pb, A, slot, lane, sidx);
     } else {
         if (need) lb_emit<kB>(c, dx, pen, pb, pp, A, slot, lane, sidx);
     }
@@ -513,6 +514,84 @@ int launch_lb_step(hipStream_t st, const LbArgs& A, int n_live, bool batch = fal
     return launch_lb_step_as<false, false>(st, A, n_live);
 }
 
+
+// ---- Levenberg-Marquardt (dh_calibrate_lm_batch; dh_lm.h) -------------------------
+// Global state of one start: the LmCore as it is (all doubles, then the scalars).
+using LmSlot = dhlm::LmCore;
+static_assert(sizeof(LmSlot) % 8 == 0 && std::is_trivially_copyable<LmSlot>::value,
+              "lm_step_kernel copies the state as 8-byte words");
+constexpr int kLmWords = (int)(sizeof(LmSlot) / 8);
+
+// One wave per live start, as lb_step_kernel's kG build: stage the state in LDS (coalesced), consume
+// the finished request -- f (A.sse), g (A.grad) and the Gauss-Newton Hessian (hess) of the slot,
+// from dh_gauss_newton.h's reduction -- run the state machine in lane 0 (plain scalar code, the CPU
+// build's: tests/native/lm_host.cpp), emit the next record with lb_emit_grad (the same transform,
+// penalty, spot, rate and row as the analytic L-BFGS-B driver's), store the state.  The live list
+// is read from memory (the host uploads it at every compaction).  The trace rows are lb_step_kernel's.
+__global__ __launch_bounds__(64) void lm_step_kernel(LbArgs A, LmSlot* __restrict__ states,
+                                                     const double* __restrict__ hess) {
+    __shared__ LmSlot c;
+    __shared__ double pb[dhlb::kLanes];
+    __shared__ int need_s;
+    const int slot = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int sidx = A.live[slot];
+    unsigned long long* const G = (unsigned long long*)(states + sidx);
+    unsigned long long* const cw = (unsigned long long*)&c;
+    if (A.mode == 0) {
+        if (lane == 0) dhlm::lm_begin(c, A.x0 + (size_t)sidx * dhlm::kN);
+    } else {
+        for (int i = lane; i < kLmWords; i += 64) cw[i] = G[i];
+    }
+    __syncthreads();
+    if (A.mode != 0 && c.s.done) return;               // uniform across the wave
+    int need = 1;
+    if (A.mode == 1) {
+        const double f = A.sse[slot];
+        const double* ge = A.grad + (size_t)slot * dhlm::kN;
+        if (A.trace) {
+            unsigned long long k = 0;
+            if (lane == 0) k = atomicAdd(A.trace_n, 1ull);
+            k = __shfl(k, 0, 64);
+            if ((int64_t)k < A.trace_cap) {
+                double* tr = A.trace + k * kLbTrace;
+                if (lane == 0) {
+                    tr[0] = sidx;
+                    tr[1] = c.s.n_calls;
+                    tr[2] = f;
+                    tr[3 + 2 * dhlm::kN] = A.market_of[sidx];
+                }
+                if (lane < dhlm::kN) {
+                    tr[3 + lane] = c.xe[lane];
+                    tr[3 + dhlm::kN + lane] = ge[lane];
+                }
+            }
+        }
+        if (lane == 0) {
+            const dhlm::LmConfig cf{A.cfg.maxiter, A.cfg.maxfun, A.cfg.factr_epsmch, A.cfg.pgtol};
+            need_s = dhlm::lm_resume(c, cf, f, ge, hess + (size_t)slot * (dhlm::kN * dhlm::kN));
+            if (!need_s) {
+                __hip_atomic_store(&A.done[sidx], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                atomicSub(A.live_count, 1);
+            }
+        }
+        __syncthreads();
+        need = need_s;
+    }
+    if (need) {
+        WaveVec dx, pen;
+        lb_emit_grad(lane < dhlm::kN ? c.xe[lane] : 0.0, dx, pen, pb, A, slot, lane, sidx);
+    }
+    __syncthreads();
+    for (int i = lane; i < kLmWords; i += 64) G[i] = cw[i];
+}
+
+int launch_lm_step(hipStream_t st, const LbArgs& A, int n_live, LmSlot* states, const double* hess) {
+    hipLaunchKernelGGL(lm_step_kernel, dim3((unsigned)n_live), dim3(64), 0, st, A, states, hess);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
+}
+
 // the markets of dh_calibrate_lbfgs_batch (host arrays): mkt [B][M], spot [B], rate [B] and the
 // market of each start
 struct LbBatch {
@@ -528,6 +607,9 @@ struct LbBatch {
     // dh_calibrate_lbfgs_batch_grad: one analytic loss + gradient request per iteration; with
     // the weights, dh_calibrate_lbfgs_batch_iv_grad: the vol objective's (dh_iv_grad.h)
     bool grad = false;
+    // dh_calibrate_lm_batch (with grad): the same request through dh_gauss_newton.h's reduction,
+    // which adds the Gauss-Newton Hessian, and lm_step_kernel in place of lb_step_kernel
+    bool lm = false;
 };
 
 }  // namespace
@@ -547,6 +629,7 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
     int rc = check_N(N);
     if (rc) return rc;
     const bool grad = bt && bt->grad;
+    const bool lm = grad && bt->lm;
     if (grad && N > DH_PARAM_GRAD_MAX_N)
         return fail(DH_E_ARG, "N must be in [1, " + std::to_string(DH_PARAM_GRAD_MAX_N) +
                                   "] under the analytic gradient, got " + std::to_string(N));
@@ -577,7 +660,8 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t st = ctx->stream;
     const size_t npts = (size_t)S * dhlb::kPts;
-    HIP_TRY(ctx->lb_state.reserve((size_t)S * sizeof(LbSlot)));
+    const size_t slot_bytes = lm ? sizeof(LmSlot) : sizeof(LbSlot);
+    HIP_TRY(ctx->lb_state.reserve((size_t)S * slot_bytes));
     HIP_TRY(ctx->lb_rec.reserve(npts * DH_PARAM_STRIDE * 8));
     HIP_TRY(ctx->lb_sse.reserve(npts * 8));
     HIP_TRY(ctx->lb_bad.reserve(npts * 4));
@@ -602,8 +686,11 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
         HIP_TRY(ctx->rows_row.reserve(npts * 4));
         if (grad)   // once, for all S starts: the gradients [S][16], penalties [S], planes [14][S][M]
                     // and under the vol objective the c_m plane [S][M] (dh_iv_grad.h)
-            HIP_TRY(ctx->pg_scratch.reserve(bt->iv_wgt ? dhivg::scratch_bytes(S, M)
-                                                       : dhpg::loss_grad_scratch(S, M)));
+                    // and under Levenberg-Marquardt the Hessians [S][13][13] after the planes
+            HIP_TRY(ctx->pg_scratch.reserve(
+                bt->iv_wgt ? dhivg::scratch_bytes(S, M)
+                           : dhpg::loss_grad_scratch(S, M) +
+                                 (lm ? (size_t)S * dhlm::kN * dhlm::kN * 8 : 0)));
         else
             HIP_TRY(ctx->lb_prices.reserve(npts * M * 8));
         HIP_TRY(ctx->lb_spot.reserve((size_t)S * 8));
@@ -690,14 +777,20 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
     double* const d_pen = grad ? d_grad + (size_t)S * DH_PARAM_STRIDE : nullptr;
     double* const d_planes = grad ? d_pen + S : nullptr;
     double* const d_cm = grad && iv ? d_planes + (size_t)dhpg::kPlanes * S * M : nullptr;
+    double* const d_hess = lm ? d_planes + (size_t)dhpg::kPlanes * S * M : nullptr;
     A.grad = d_grad;
     A.pen_out = d_pen;
     auto set_inline = [&](const int* lst, int n) {
-        A.n_inline = n <= kLbInline ? 1 : 0;
+        A.n_inline = !lm && n <= kLbInline ? 1 : 0;   // lm_step_kernel reads the list from memory
         for (int i = 0; i < kLbInline; ++i) A.live_inline[i] = i < n && A.n_inline ? lst[i] : 0;
     };
+    // the seam between the two optimisers: which step kernel advances the live starts
+    auto launch_step = [&](int n) -> int {
+        return lm ? launch_lm_step(st, A, n, (LmSlot*)ctx->lb_state.ptr, d_hess)
+                  : launch_lb_step(st, A, n, batch, iv, grad);
+    };
     set_inline(h_live[0], S);
-    rc = launch_lb_step(st, A, S, batch, iv, grad);
+    rc = launch_step(S);
     if (rc) return rc;
 
     // Chunks of `chunk` iterations (loss launch(es) + step launch) are enqueued two ahead of the
@@ -718,7 +811,13 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
             if (grad) {
                 // the planes of the live starts' records, then each set's loss and gradient
                 // against its start's market row; the step reads them finished
-                if (iv)                                // rows_mkt holds vols
+                if (lm)
+                    e = dhgn::gauss_newton_rows_launch(ctx, s, A.rec, d_pen,
+                                                       (const double*)ctx->rows_mkt.ptr, A.row,
+                                                       n_live, N, L, d_planes, (double*)A.sse,
+                                                       d_grad, (int*)A.bad, d_hess, st,
+                                                       A.live_count);
+                else if (iv)                           // rows_mkt holds vols
                     e = dhivg::loss_iv_grad_rows_launch(
                         ctx, s, A.rec, d_pen, (const double*)ctx->rows_mkt.ptr,
                         (const double*)ctx->rows_wgt.ptr, A.row, (const double*)ctx->lb_wsum.ptr,
@@ -730,7 +829,7 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
                                                     n_live, N, L, d_planes, (double*)A.sse, d_grad,
                                                     (int*)A.bad, st, A.live_count);
                 if (e) return e;
-                e = launch_lb_step(st, A, n_live, true, false, true);
+                e = launch_step(n_live);
                 if (e) return e;
                 ++launches;
                 continue;
@@ -810,17 +909,37 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
                                        hipMemcpyHostToDevice, st));
             }
             A.mode = 2;
-            rc = launch_lb_step(st, A, n_live, batch, iv, grad);
+            rc = launch_step(n_live);
             if (rc) return rc;
         }
         rc = enqueue_chunk(k + 2);
         if (rc) return rc;
     }
-    std::vector<LbSlot> hs(S);
-    HIP_TRY(hipMemcpyAsync(hs.data(), ctx->lb_state.ptr, (size_t)S * sizeof(LbSlot),
-                           hipMemcpyDeviceToHost, st));
+    std::vector<unsigned char> hbytes((size_t)S * slot_bytes);
+    HIP_TRY(hipMemcpyAsync(hbytes.data(), ctx->lb_state.ptr, hbytes.size(), hipMemcpyDeviceToHost,
+                           st));
     HIP_TRY(hipStreamSynchronize(st));
     drain.armed = false;
+    if (n_launches) *n_launches = (int32_t)launches;
+    if (lm) {
+        const LmSlot* hl = (const LmSlot*)hbytes.data();
+        for (int i = 0; i < S; ++i) {
+            const dhlm::LmScalars& q = hl[i].s;
+            dh_lb_result& o = out[i];
+            for (int j = 0; j < dhlm::kN; ++j) o.x[j] = hl[i].x[j];
+            o.fun = q.f;
+            o.best_loss = q.best_loss;
+            o.t_done = t_done[i];
+            o.nit = q.nit;
+            o.nfev = q.nfev;
+            o.task = q.task;
+            o.warnflag = q.warnflag;
+            o.n_calls = q.n_calls;
+            o.pad = 0;
+        }
+        return DH_OK;
+    }
+    const LbSlot* hs = (const LbSlot*)hbytes.data();
     for (int i = 0; i < S; ++i) {
         const LbSlot& q = hs[i];
         dh_lb_result& o = out[i];
@@ -835,7 +954,6 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
         o.n_calls = q.s.n_calls;
         o.pad = 0;
     }
-    if (n_launches) *n_launches = (int32_t)launches;
     return DH_OK;
 }
 
@@ -905,6 +1023,20 @@ extern "C" int dh_calibrate_lbfgs_batch_iv_grad(dh_ctx* ctx, const dh_surface* s
     bt.iv_wgt = w.data();
     bt.iv_wsum = wsum.data();
     bt.grad = true;
+    return lb_run(ctx, s, x0, S, 0.0, 0.0, N, L, opt, out, n_launches, &bt);
+}
+
+// Levenberg-Marquardt on the Gauss-Newton Hessian: dh_calibrate_lbfgs_batch_grad's arguments, checks
+// and host loop; the iteration is the planes launch, dh_gauss_newton.h's reduction and
+// lm_step_kernel (dh_lm.h).
+extern "C" int dh_calibrate_lm_batch(dh_ctx* ctx, const dh_surface* s, const double* mkt,
+                                     const double* spot, const double* rate, int B,
+                                     const double* x0, const int32_t* market_of, int S, int N,
+                                     double L, const dh_lb_options* opt, dh_lb_result* out,
+                                     int32_t* n_launches) {
+    LbBatch bt{mkt, spot, rate, B, market_of};
+    bt.grad = true;
+    bt.lm = true;
     return lb_run(ctx, s, x0, S, 0.0, 0.0, N, L, opt, out, n_launches, &bt);
 }
 

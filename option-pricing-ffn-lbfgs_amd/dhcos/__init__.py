@@ -8,7 +8,10 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
     generate_synthetic_calibrations   src/data/synthetic_generator.py
     implied_vol                       (new: Black-Scholes implied volatility of prices)
     calibrate_batch                   (new: many markets on one option grid, calibrated together;
-                                       gradient="analytic" runs them on the exact loss gradient)
+                                       gradient="analytic" runs them on the exact loss gradient,
+                                       method="lm" by Levenberg-Marquardt on the Gauss-Newton
+                                       Hessian; result.uncertainty() gives the parameters'
+                                       covariance, standard errors and conditioning)
     monte_carlo                       (new: path pricing of European, Asian and barrier options,
                                        with antithetic pairs and COS-priced control variates)
     american_monte_carlo              (new: American and Bermudan options by least-squares Monte Carlo)
@@ -27,7 +30,7 @@ torch) shards starts / samples over ``torch.distributed`` ranks (one process per
 from .pricer import DoubleHeston, implied_vol
 from .calibrator import CalibrationResult, DoubleHestonJumpCalibrator
 from .generator import generate_synthetic_calibrations
-from .batch import BatchCalibrationResult, calibrate_batch
+from .batch import BatchCalibrationResult, ParameterUncertainty, calibrate_batch
 from .montecarlo import MonteCarloResult, VarianceReducedResult, monte_carlo
 from .american import AmericanMonteCarloResult, american_monte_carlo
 from .greeks import Greeks, greeks
@@ -39,5 +42,5 @@ __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
            "BatchCalibrationResult", "monte_carlo", "MonteCarloResult",
            "VarianceReducedResult",
            "american_monte_carlo", "AmericanMonteCarloResult", "greeks", "Greeks",
-           "parameter_sensitivities", "ParameterSensitivities"]
+           "parameter_sensitivities", "ParameterSensitivities", "ParameterUncertainty"]
 __version__ = "0.1.0"

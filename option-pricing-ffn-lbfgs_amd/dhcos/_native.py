@@ -49,6 +49,14 @@ GREEKS = ("price", "delta", "gamma", "dual_delta", "vega1", "vega2")
 PARAM_SENS = ("price", "v1_0", "kappa1", "theta1", "sigma1", "rho1", "v2_0", "kappa2", "theta2",
               "sigma2", "rho2", "lambda_j", "mu_j", "sigma_j")
 PARAM_GRAD_MAX_N = 1024
+# dh_lb_result.task of a Levenberg-Marquardt start (the header's DH_LM_* enum) -> its message
+LM_MESSAGES = {1: "CONVERGENCE: MAX GRADIENT COMPONENT <= GTOL",
+               2: "CONVERGENCE: RELATIVE REDUCTION OF F <= FTOL",
+               3: "CONVERGENCE: STEP <= XTOL",
+               4: "STOP: ACCEPTED STEPS REACHED MAXITER",
+               5: "STOP: REQUESTS REACHED MAXFUN",
+               6: "ABNORMAL: DAMPING PAST ITS CEILING",
+               7: "ABNORMAL: INVALID LOSS AT X0"}
 
 _dp = C.POINTER(C.c_double)
 _i8p = C.POINTER(C.c_int8)
@@ -203,6 +211,13 @@ SIGNATURES = {
                                             _int, _dbl, _vp, _vp, _vp, _vp]),
     "dh_calibrate_lbfgs_batch_iv_grad": (_int, [_vp, _vp, _dp, _dp, _dp, _dp, _int, _dp, _i32p,
                                                 _int, _int, _dbl, _lbo, _lbr, _i32p]),
+    # ---- Gauss-Newton Hessian and Levenberg-Marquardt
+    "dh_surface_gauss_newton_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int,
+                                            _dbl, _vp, _vp, _vp, _vp]),
+    "dh_surface_gauss_newton_rows_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int,
+                                                _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "dh_calibrate_lm_batch": (_int, [_vp, _vp, _dp, _dp, _dp, _int, _dp, _i32p, _int, _int, _dbl,
+                                     _lbo, _lbr, _i32p]),
     # ---- building blocks
     "dh_cf": (_int, [_vp, _dp, _dp, _int, _dbl, _dp, _dp]),
     "dh_cf_complex": (_int, [_vp, _dp, _dp, _dp, _int, _dbl, _dp, _dp]),
@@ -1200,6 +1215,51 @@ class Surface(_Handle):
                       (_ptr(mkt), _ptr(spots), _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p), S,
                        int(N), float(L)), maxiter, maxfun, maxls, chunk, ftol, gtol)
 
+    def gauss_newton_rows(self, X, mkt, spots, rates, row, N=128, L=10.0):
+        """dh_surface_gauss_newton_rows: loss_grad_rows with the Gauss-Newton Hessian of the price
+        part of the loss in the optimiser's x -> (f [S], g [S, 13], bad [S], H [S, 13, 13]); f, g
+        and bad are loss_grad_rows's bits, H is exactly symmetric, and an invalid set has H = 0."""
+        X = _f64(X).reshape(-1, 13)
+        S = X.shape[0]
+        mkt = self._market_rows(mkt)
+        B = mkt.shape[0]
+        spots, rates = _f64(spots).reshape(-1), _f64(rates).reshape(-1)
+        if spots.size != B or rates.size != B:
+            raise ValueError("mkt, spots and rates differ in length")
+        row = np.ascontiguousarray(row, dtype=np.int32).reshape(-1)
+        if row.size != S:
+            raise ValueError("X and row differ in length")
+        f, g, bad = np.empty(S), np.empty((S, 13)), np.empty(S, dtype=np.int32)
+        H = np.empty((S, 13, 13))
+        with self.ctx._lock:
+            _check(load().dh_surface_gauss_newton_rows(
+                self.ctx.handle, self._h, _addr(X, S), _addr(mkt, B), _addr(spots, B),
+                _addr(rates, B), _addr(row, S), S, B, int(N), float(L), f.ctypes.data,
+                g.ctypes.data, bad.ctypes.data, H.ctypes.data))
+        return f, g, bad, H
+
+    def gauss_newton_rows_dev(self, d_x: int, d_mkt: int, d_spot: int, d_rate: int, d_row: int,
+                              S: int, d_f: int, d_g: int, d_bad: int, d_H: int, N=128, L=10.0,
+                              stream: int = 0):
+        """dh_surface_gauss_newton_rows_dev: loss_grad_rows_dev's arguments and d_H [S, 13, 13]
+        out, enqueued on stream."""
+        _check(load().dh_surface_gauss_newton_rows_dev(
+            self.ctx.handle, self._h, _addr(d_x), _addr(d_mkt), _addr(d_spot), _addr(d_rate),
+            _addr(d_row), int(S), int(N), float(L), _addr(d_f), _addr(d_g), _addr(d_bad),
+            _addr(d_H), _addr(stream)))
+
+    def calibrate_lm_batch(self, mkt, spots, rates, x0s, market_of, N=128, L=10.0, *,
+                           maxiter=300, maxfun=15000, ftol=1e-9, gtol=1e-6, chunk=8, ctx=None):
+        """calibrate_lbfgs_batch_grad's markets and starts under Levenberg-Marquardt on the
+        Gauss-Newton Hessian (dh_calibrate_lm_batch): one request per iteration (n_calls == nfev),
+        nit accepted steps, task an LM_* code, N <= PARAM_GRAD_MAX_N.
+        -> (list of LbResult, number of iterations enqueued)."""
+        mkt, spots, rates, x0s, mof = lb_batch_args(self.M, mkt, spots, rates, x0s, market_of)
+        B, S = mkt.shape[0], x0s.shape[0]
+        return _lbfgs("dh_calibrate_lm_batch", ctx or self.ctx, self, S,
+                      (_ptr(mkt), _ptr(spots), _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p), S,
+                       int(N), float(L)), maxiter, maxfun, 20, chunk, ftol, gtol)
+
     def iv_grad_rows_dev(self, d_planes: int, d_params: int, d_pen: int, d_mkt_iv: int, d_wgt: int,
                          d_row: int, d_div: int, S: int, d_f: int, d_g: int, d_bad: int,
                          d_sse: int = 0, d_iv: int = 0, stream: int = 0):
@@ -1795,7 +1855,7 @@ __all__ = [
     "resolve_device", "default_context", "PARAM_STRIDE", "MAX_N", "MAX_N_PER_TERM",
     "STRIKE_ABSOLUTE", "STRIKE_PCT_SPOT", "PATH_AUTO", "PATH_SPLIT", "PATH_FUSED", "PATH_GEN",
     "FG_SLOTS", "STAMPS_PER_BLOCK", "GREEKS", "PARAM_SENS", "PARAM_GRAD_MAX_N",
-    "Context", "Surface", "FgChannel", "pinned", "pinned_empty", "host_cache_trim",
+    "LM_MESSAGES", "Context", "Surface", "FgChannel", "pinned", "pinned_empty", "host_cache_trim",
     "LbOptions", "LbResult", "lb_batch_args", "iv_rows",
     "gen_draw", "GenDraw", "GEN_LOC_WORDS", "gen_locate", "gen_draw_located", "gen_sweep",
     "gen_drawn_samples", "gen_dates", "gen_assemble", "gen_device", "gen_log",

@@ -38,13 +38,79 @@ from .pricer import implied_vol, resolve_call
 OBJECTIVES = ("price", "iv")
 GRADIENTS = ("fd", "analytic")
 IV_GRADIENTS = ("fd", "vega")                          # objective="iv"'s
+METHODS = ("lbfgs", "lm")
 
 FAILED_MESSAGE = "All optimization starts failed"      # lbfgs_calibrator.py:318-333
+RANK_RCOND = 1e-12      # uncertainty(): eigenvalues of H at or below this share of the largest are cut
 
 
-def task_message(task: int) -> str:
-    """SciPy's message for a task code status * 1000 + message (dh_lb_result.task)."""
+def task_message(task: int, method: str = "lbfgs") -> str:
+    """SciPy's message for a task code status * 1000 + message (dh_lb_result.task); under
+    method="lm" the message of a DH_LM_* code."""
+    if method == "lm":
+        return _native.LM_MESSAGES[int(task)]
     return status_messages[int(task) // 1000] + ": " + task_messages[int(task) % 1000]
+
+
+@dataclass
+class ParameterUncertainty:
+    """BatchCalibrationResult.uncertainty()'s result, arrays over markets [B]; NaN (rank -1) where
+    a market has no winner or its winner's loss is invalid."""
+    hessian: np.ndarray          # [B, 13, 13] Gauss-Newton Hessian of the price loss in x
+    covariance_x: np.ndarray     # [B, 13, 13] 2 f / dof pinv(H), in the optimiser's x
+    covariance: np.ndarray       # [B, 13, 13] the same in model parameters: J covariance_x J
+    stderr: np.ndarray           # [B, 13] sqrt of covariance's diagonal
+    condition: np.ndarray        # [B] largest / smallest eigenvalue of H (inf: not positive)
+    weakest: np.ndarray          # [B, 13] unit eigenvector of H's smallest eigenvalue, in x
+    rank: np.ndarray             # [B] eigenvalues above RANK_RCOND times the largest
+    dof: int                     # max(M - 13, 1)
+
+
+def transform_jacobian(x) -> np.ndarray:
+    """d(model parameter)/dx of x [..., 13], the transform's diagonal: 1 - tanh(x)^2 for the two
+    correlations, 1 for mu_j, exp(x) otherwise."""
+    x = np.asarray(x, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        j = np.exp(x)
+    j[..., [4, 9]] = 1.0 - np.tanh(x[..., [4, 9]]) ** 2
+    j[..., 11] = 1.0
+    return j
+
+
+def gauss_newton_uncertainty(H, f, x, M, valid=None) -> ParameterUncertainty:
+    """The 13 x 13 algebra of uncertainty() on the host (NumPy): H [B, 13, 13] symmetric, f [B]
+    the losses, x [B, 13] the points, M the options per market, valid [B] bool (default all).
+    With H = V diag(e) V', the eigenvalues e_k <= RANK_RCOND max(e) are cut: rank counts the rest,
+    pinv(H) = sum_kept v_k v_k' / e_k, covariance_x = 2 f / dof pinv(H) with dof = max(M - 13, 1)
+    (sigma^2 (J'J)^-1 for this loss: f = RSS / M and H = 2 J'J / M), condition = max(e) / min(e)
+    (inf where min(e) <= 0) and weakest = the eigenvector of min(e), its largest component
+    positive."""
+    H = np.asarray(H, dtype=np.float64)
+    B = H.shape[0]
+    f, x = np.asarray(f, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    valid = np.ones(B, dtype=bool) if valid is None else np.asarray(valid, dtype=bool)
+    dof = max(int(M) - N_PARAMS, 1)
+    out = ParameterUncertainty(
+        hessian=np.where(valid[:, None, None], H, np.nan),
+        covariance_x=np.full((B, N_PARAMS, N_PARAMS), np.nan),
+        covariance=np.full((B, N_PARAMS, N_PARAMS), np.nan), stderr=np.full((B, N_PARAMS), np.nan),
+        condition=np.full(B, np.nan), weakest=np.full((B, N_PARAMS), np.nan),
+        rank=np.full(B, -1, dtype=np.int64), dof=dof)
+    for b in np.flatnonzero(valid):
+        if not np.all(np.isfinite(H[b])):
+            continue
+        e, V = np.linalg.eigh(H[b])                    # ascending
+        keep = e > RANK_RCOND * e[-1] if e[-1] > 0.0 else np.zeros(N_PARAMS, dtype=bool)
+        out.rank[b] = int(keep.sum())
+        out.condition[b] = e[-1] / e[0] if e[0] > 0.0 else np.inf
+        w = V[:, 0]
+        out.weakest[b] = w if w[np.argmax(np.abs(w))] > 0.0 else -w
+        pinv = (V[:, keep] / e[keep]) @ V[:, keep].T
+        out.covariance_x[b] = (2.0 * f[b] / dof) * pinv
+        j = transform_jacobian(x[b])
+        out.covariance[b] = j[:, None] * out.covariance_x[b] * j[None, :]
+        out.stderr[b] = np.sqrt(np.diag(out.covariance[b]))
+    return out
 
 
 def pick_winners(fun) -> np.ndarray:
@@ -99,9 +165,46 @@ class BatchCalibrationResult:
     # "fd": 14 loss evaluations per request; "analytic" and "vega": one (n_calls == nfev)
     gradient: str = "fd"
     loss_evals: int = 0              # loss evaluations of the whole call: n_calls summed
+    # "lbfgs": task holds SciPy's codes; "lm": the DH_LM_* codes, and success is a tolerance stop
+    method: str = "lbfgs"
+    grid: tuple = None               # calibrate_batch's option grid, _surface's arguments
 
     def message(self, b: int) -> str:
-        return task_message(self.task[b]) if self.best_start[b] >= 0 else FAILED_MESSAGE
+        if self.best_start[b] < 0:
+            return FAILED_MESSAGE
+        return task_message(self.task[b], self.method)
+
+    def uncertainty(self, N=128, device=None) -> ParameterUncertainty:
+        """How well each market determines its calibrated parameters: one
+        Surface.gauss_newton_rows call at the winners' x, then 13 x 13 algebra on the host
+        (gauss_newton_uncertainty) -> ParameterUncertainty.  Works after either method, for the
+        price objective (the Hessian is the price loss's).
+
+        What the numbers are: a LOCAL estimate at the returned x, from the GAUSS-NEWTON Hessian
+        H = 2 J'J / M of the relative price errors (second derivatives of the prices and the Feller
+        penalty's curvature are left out), with the COS series' truncation range held FIXED as the
+        parameter sensitivities hold it.  covariance_x = 2 f / dof pinv(H), dof = max(M - 13, 1),
+        is the usual sigma^2 (J'J)^-1 with the residual variance estimated from the fit itself; it
+        says how far the parameters could move before the fit degrades as much as it already
+        misses, not how far they are from a true model.  Directions whose eigenvalue is at or below
+        RANK_RCOND of the largest are cut from pinv (rank < 13): the standard errors then cover
+        the retained directions only.  Markets with no winner get NaN and rank -1."""
+        if self.grid is None:
+            raise ValueError("uncertainty() needs the option grid of a calibrate_batch result")
+        if self.objective != "price":
+            raise ValueError("uncertainty() is the price objective's")
+        surf = _surface(_native.default_context(device), *self.grid)
+        B = self.x.shape[0]
+        won = np.flatnonzero(self.best_start >= 0)
+        H = np.full((B, N_PARAMS, N_PARAMS), np.nan)
+        f = np.full(B, np.nan)
+        valid = np.zeros(B, dtype=bool)
+        if won.size:
+            fw, _, bad, Hw = surf.gauss_newton_rows(self.x[won], self.market_prices, self.spots,
+                                                    self.risk_free, won.astype(np.int32), N)
+            H[won], f[won] = Hw, fw
+            valid[won] = (bad == 0) & np.isfinite(fw)
+        return gauss_newton_uncertainty(H, f, self.x, self.market_prices.shape[1], valid)
 
     def market_options(self, b: int):
         return [{"strike": float(k), "maturity": float(t), "price": float(p),
@@ -192,6 +295,25 @@ def check_gradient(gradient, objective, N):
             raise ValueError(f"gradient={gradient!r}: N must be a whole number in "
                              f"[1, {_native.PARAM_GRAD_MAX_N}], got {N!r}")
     return gradient
+
+
+def check_method(method, gradient, objective, N):
+    """The optimiser switch of calibrate_batch, or ValueError.  "lm" fits the price objective on
+    its analytic Jacobian, whatever `gradient` says -- except "vega", the vol objective's -- on
+    series of at most PARAM_GRAD_MAX_N terms."""
+    if method not in METHODS:
+        raise ValueError(f"method must be 'lbfgs' or 'lm', not {method!r}")
+    if method == "lm":
+        if objective != "price":
+            raise ValueError("method='lm' fits the price objective only; objective='iv' runs "
+                             "method='lbfgs'")
+        if gradient == "vega":
+            raise ValueError("gradient='vega' differentiates the vol objective; method='lm' "
+                             "fits the price objective on its analytic Jacobian")
+        if not (isinstance(N, (int, np.integer)) and 1 <= N <= _native.PARAM_GRAD_MAX_N):
+            raise ValueError(f"method='lm': N must be a whole number in "
+                             f"[1, {_native.PARAM_GRAD_MAX_N}], got {N!r}")
+    return method
 
 
 def check_iv_market(market_ivs, iv_weights, B, M):
@@ -285,7 +407,8 @@ def _surface(ctx, K, T, flags, mode, strikes_pct, maturities):
 
 def summarize(mkt, sp, r, Kabs, T, flags, X, fun, nit, nfev, task, status, best_loss, n_calls,
               t_done, model_prices_of, enqueued=0, *, objective="price", market_ivs=None,
-              iv_weights=None, gradient="fd") -> BatchCalibrationResult:
+              iv_weights=None, gradient="fd", method="lbfgs",
+              grid=None) -> BatchCalibrationResult:
     """Per-market rows from per-start results [B, S]: the winner of each market
     (pick_winners), re-priced by model_prices_of(params [W, 13], markets [W]) -> [W, M] in one
     call; a market without a winner gets the reference's failure row (zeros, inf, success
@@ -324,13 +447,14 @@ def summarize(mkt, sp, r, Kabs, T, flags, X, fun, nit, nfev, task, status, best_
         start_task=task, status=status, best_loss=best_loss, n_calls=n_calls, start_x=X,
         iterations_enqueued=enqueued, objective=objective, market_ivs=market_ivs,
         iv_weights=iv_weights, model_ivs=model_iv, gradient=gradient,
-        loss_evals=int(np.sum(n_calls)))
+        loss_evals=int(np.sum(n_calls)), method=method, grid=grid)
 
 
 def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
                     maturities=MATURITIES, strikes=None, is_call=True, x0s=None, multi_start=3,
                     maxiter=300, N=128, device=None, chunk=8, objective="price",
-                    market_ivs=None, iv_weights=None, gradient="fd") -> BatchCalibrationResult:
+                    market_ivs=None, iv_weights=None, gradient="fd",
+                    method="lbfgs") -> BatchCalibrationResult:
     """Calibrate B markets that share one option grid, all starts of all markets together in the
     device-resident L-BFGS-B.
 
@@ -367,9 +491,23 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
     (dh_calibrate_lbfgs_batch_iv_grad: each option's price sensitivities divided by its
     Black-Scholes vega at the model vol); N <= 1024, n_calls == nfev.  An option whose model price
     sits at its lower bound (vol 0.0) adds its residual to the loss and nothing to the gradient,
-    the one-sided rule of the Feller kink."""
+    the one-sided rule of the Feller kink.
+
+    method="lbfgs" (the default): the device-resident L-BFGS-B, as above.  method="lm":
+    Levenberg-Marquardt on the Gauss-Newton Hessian of the price loss (dh_calibrate_lm_batch,
+    DESIGN.md 3.21): every request is the parameter planes, reduced to the loss, its gradient and
+    the 13 x 13 Hessian, and one damped Cholesky step.  The price objective only, N <= 1024; the
+    Jacobian is always the analytic planes, so `gradient` is not consulted (gradient="vega" and
+    objective="iv" raise ValueError).  nit counts accepted steps, nfev == n_calls requests; the
+    returned x is the last accepted point, so fun never exceeds the start's loss; task holds an
+    LM_* code (result.message(b) names it) and success means a tolerance stop.
+
+    result.uncertainty() estimates, after either method, how well each market determines its
+    parameters."""
     check_objective(objective)
-    check_gradient(gradient, objective, N)
+    check_method(method, gradient, objective, N)
+    if method == "lbfgs":
+        check_gradient(gradient, objective, N)
     if objective == "price" and (market_ivs is not None or iv_weights is not None):
         raise ValueError("market_ivs and iv_weights belong to objective='iv'")
     K, T, flags, mode = _grid(strikes_pct, maturities, strikes, is_call)
@@ -398,7 +536,8 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
         res, enqueued = run(ivs, wts, sp, r, X.reshape(B * S, N_PARAMS), market_of, N,
                             maxiter=maxiter, maxfun=_MAXFUN, chunk=chunk)
     else:
-        run = (surf.calibrate_lbfgs_batch_grad if gradient == "analytic"
+        run = (surf.calibrate_lm_batch if method == "lm"
+               else surf.calibrate_lbfgs_batch_grad if gradient == "analytic"
                else surf.calibrate_lbfgs_batch)
         res, enqueued = run(mkt, sp, r, X.reshape(B * S, N_PARAMS), market_of, N,
                             maxiter=maxiter, maxfun=_MAXFUN, chunk=chunk)
@@ -423,4 +562,5 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
                      col("warnflag", np.int64), col("best_loss", np.float64),
                      col("n_calls", np.int64), col("t_done", np.float64), model_prices_of,
                      enqueued, objective=objective, market_ivs=ivs, iv_weights=wts,
-                     gradient=gradient)
+                     gradient="analytic" if method == "lm" else gradient, method=method,
+                     grid=(K, T, flags, mode, strikes_pct, maturities))
