@@ -747,6 +747,46 @@ int dh_calibrate_lm_batch(dh_ctx* ctx, const dh_surface* s, const double* mkt, c
                           int S, int N, double L, const dh_lb_options* opt, dh_lb_result* out,
                           int32_t* n_launches);
 
+/* ---- warm-start network: a feed-forward net from a market's prices to an optimiser start ------
+ * x0 [13] = y_mean + y_std * net(((C p) / S0 - x_mean) / x_std): p [M] the market's prices, C
+ * [F][M] the (linear) feature matrix, net a stack of n_layers - 1 hidden layers (ReLU) and a linear
+ * output of DH_FFN_OUT values, BatchNorm already folded into its float weights.  The output is the
+ * optimiser's unconstrained x (log / arctanh / identity of the 13 model parameters): it goes into
+ * dh_calibrate_lbfgs_batch* and dh_calibrate_lm_batch as x0s, unchanged.
+ * Arithmetic (one launch): each feature is an fp64 fma chain over j ascending,
+ * divided by S0, standardised and rounded once to float; every neuron is one float fmaf chain from
+ * its bias over k ascending (v_mfma_f32_32x32x2_f32, exact f32), ReLU = fmaxf(0, .); the output is
+ * fma(y_std, (double)raw, y_mean) in fp64.  A market's result depends on nothing but its own row:
+ * not on B, not on its place in the batch.                                                     */
+enum {
+    DH_FFN_OUT = 13,             /* outputs: the optimiser's x */
+    DH_FFN_TM = 32,              /* markets per block */
+    DH_FFN_MAX_HIDDEN = 6,       /* hidden layers at most (at least 1) */
+    DH_FFN_MAX_WIDTH = 512,      /* hidden widths: multiples of 32 in [32, DH_FFN_MAX_WIDTH] */
+    DH_FFN_MAX_IN = 64           /* F and M at most */
+};
+typedef struct dh_ffn dh_ffn;
+/* widths [n_layers + 1] = F, the hidden widths, DH_FFN_OUT; weights the layers' W_l [out][in]
+ * row-major one after the other, biases likewise; C [F][M]; x_mean, x_std [F]; y_mean, y_std
+ * [DH_FFN_OUT].  Everything is copied to the device once (layers transposed and zero-padded: F up
+ * to a multiple of 8, the outputs up to 32).  DH_E_ARG for n_layers outside [2, DH_FFN_MAX_HIDDEN + 1], F or
+ * M outside [1, DH_FFN_MAX_IN], a hidden width that is no multiple of 32 in [32,
+ * DH_FFN_MAX_WIDTH], a last width other than DH_FFN_OUT, x_std not finite and > 0, or any other
+ * statistic not finite.  The object belongs to ctx: no forward call after the context is gone (dh_ffn_destroy alone needs no live context). */
+int dh_ffn_create(dh_ctx* ctx, int n_layers, const int* widths, const float* weights,
+                  const float* biases, const double* C, int M, const double* x_mean,
+                  const double* x_std, const double* y_mean, const double* y_std, dh_ffn** out);
+int dh_ffn_destroy(dh_ffn* ffn);
+/* market [B][M], spots [B] -> x0 [B][DH_FFN_OUT] and, unless NULL, raw [B][DH_FFN_OUT] (the
+ * network's standardised float output).  Host arrays, synchronous.  The values are the caller's
+ * promise: finite prices and spots > 0 (the Python layer checks them).                          */
+int dh_ffn_forward(dh_ffn* ffn, const double* market, const double* spots, int64_t B, double* x0,
+                   float* raw);
+/* The same over device pointers (d_raw may be NULL): one launch enqueued on `stream` (hipStream_t;
+ * NULL = the context's), no synchronisation, no allocation, no host round trip; the same bits.  */
+int dh_ffn_forward_dev(dh_ffn* ffn, const double* d_market, const double* d_spots, int64_t B,
+                       double* d_x0, float* d_raw, void* stream);
+
 /* ---- building blocks (exposed for API parity with the reference's public methods) -------- */
 /* phi(u_j; tau) for one param set: DoubleHeston.characteristic_function (double_heston.py:48-97) */
 int dh_cf(dh_ctx* ctx, const double* params, const double* u, int n, double tau, double* re,

@@ -2836,3 +2836,4 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
 #include "dh_lb_driver.h"    // the device-resident L-BFGS-B and Levenberg-Marquardt: dh_api.h,
                              // dh_iv_loss.h, dh_loss_rows.h, dh_param_grad.h, dh_iv_grad.h,
                              // dh_gauss_newton.h
+#include "dh_ffn.h"          // the warm-start network's inference: dh_host.h

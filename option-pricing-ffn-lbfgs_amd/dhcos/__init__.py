@@ -15,6 +15,10 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
     monte_carlo                       (new: path pricing of European, Asian and barrier options,
                                        with antithetic pairs and COS-priced control variates)
     american_monte_carlo              (new: American and Bermudan options by least-squares Monte Carlo)
+    FFNModel, train_ffn,              (new: the warm-start network of the reference's documents --
+    train_ffn_on_generator,            trained in PyTorch on the generator's output, evaluated by
+    fine_tune_ffn, price_features      one fused gfx950 launch; calibrate_batch(x0s=model) starts
+                                       every market from its prediction)
     greeks                            (new: analytic delta, gamma, dual delta and v0 vegas of the
                                        COS price, one pass; the module itself is dhcos/greeks.py)
     parameter_sensitivities           (new: the price's analytic sensitivity to each of the 13 model
@@ -35,6 +39,7 @@ from .montecarlo import MonteCarloResult, VarianceReducedResult, monte_carlo
 from .american import AmericanMonteCarloResult, american_monte_carlo
 from .greeks import Greeks, greeks
 from .param_sens import ParameterSensitivities, parameter_sensitivities
+from .ffn import FFNModel, fine_tune_ffn, price_features, train_ffn, train_ffn_on_generator
 from ._native import NativeError
 
 __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
@@ -42,5 +47,6 @@ __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
            "BatchCalibrationResult", "monte_carlo", "MonteCarloResult",
            "VarianceReducedResult",
            "american_monte_carlo", "AmericanMonteCarloResult", "greeks", "Greeks",
-           "parameter_sensitivities", "ParameterSensitivities", "ParameterUncertainty"]
+           "parameter_sensitivities", "ParameterSensitivities", "ParameterUncertainty",
+           "FFNModel", "train_ffn", "train_ffn_on_generator", "fine_tune_ffn", "price_features"]
 __version__ = "0.1.0"

@@ -15,6 +15,7 @@ import ctypes as C
 import os
 import sys
 import threading
+import weakref
 
 import numpy as np
 
@@ -41,6 +42,11 @@ LSM_BASIS = 10                 # DH_LSM_BASIS: regression terms
 LSM_MIN_ITM = 64               # DH_LSM_MIN_ITM: in-the-money paths a date needs to be fitted
 LSM_SLOTS = 128                # DH_LSM_SLOTS: blocks per (set, option) of a backward launch
 LSM_MAX_GIB = 16               # DH_LSM_MAX_GIB: cap of the path store
+FFN_OUT = 13                   # DH_FFN_OUT: the warm-start network's outputs, the optimiser's x
+FFN_TM = 32                    # DH_FFN_TM: markets per block of ffn_forward_kernel
+FFN_MAX_HIDDEN = 6             # DH_FFN_MAX_HIDDEN
+FFN_MAX_WIDTH = 512            # DH_FFN_MAX_WIDTH: hidden widths are multiples of 32 up to this
+FFN_MAX_IN = 64                # DH_FFN_MAX_IN: features and prices per market at most
 STAMPS_PER_BLOCK = 32          # kStamps of the DH_STAMPS build (csrc/dh_kernels.hip)
 # the planes of dh_surface_greeks / dh_greeks_pairs, in the order of the header's DH_GREEK_* enum
 GREEKS = ("price", "delta", "gamma", "dual_delta", "vega1", "vega2")
@@ -63,6 +69,7 @@ _i8p = C.POINTER(C.c_int8)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _u32p = C.POINTER(C.c_uint32)
+_f32p = C.POINTER(C.c_float)
 _vp = C.c_void_p
 
 
@@ -218,6 +225,12 @@ SIGNATURES = {
                                                 _dbl, _vp, _vp, _vp, _vp, _vp]),
     "dh_calibrate_lm_batch": (_int, [_vp, _vp, _dp, _dp, _dp, _int, _dp, _i32p, _int, _int, _dbl,
                                      _lbo, _lbr, _i32p]),
+    # ---- warm-start network
+    "dh_ffn_create": (_int, [_vp, _int, _i32p, _f32p, _f32p, _dp, _int, _dp, _dp, _dp, _dp,
+                             C.POINTER(_vp)]),
+    "dh_ffn_destroy": (_int, [_vp]),
+    "dh_ffn_forward": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "dh_ffn_forward_dev": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     # ---- building blocks
     "dh_cf": (_int, [_vp, _dp, _dp, _int, _dbl, _dp, _dp]),
     "dh_cf_complex": (_int, [_vp, _dp, _dp, _dp, _int, _dbl, _dp, _dp]),
@@ -518,6 +531,10 @@ class Context(_Handle):
             surf.close()
         for c in self.__dict__.pop("_slot_ctxs", {}).values():
             c.close()
+        for ref in self.__dict__.pop("_ffns", []):      # networks resident on this context
+            ffn = ref()
+            if ffn is not None:
+                ffn.close()
         if self._h:
             load().dh_ctx_destroy(self._h)
             self._h = None
@@ -765,6 +782,36 @@ class Context(_Handle):
                                          is_call.data_ptr(), n, out.data_ptr(), _addr(st)))
         return out
 
+    def ffn_forward_dev(self, ffn, market, spots, x0=None, raw=None, stream=None):
+        """dh_ffn_forward_dev over torch tensors on this context's device: ``ffn`` an FFN of this
+        context, market a contiguous float64 [B, M], spots float64 [B] -> x0 float64 [B, 13]
+        (``x0`` or a new tensor); ``raw`` (a float32 [B, 13] tensor, or None) receives the
+        network's standardised output.  One launch enqueued on ``stream`` (None: the context's
+        own; the null stream cannot be named, as implied_vol_dev) without synchronisation and
+        without a host round trip.  The values are the caller's promise: finite prices, spots
+        > 0."""
+        import torch
+        if ffn.ctx is not self:
+            raise ValueError("ffn_forward_dev: the network belongs to another context")
+        B = market.shape[0] if market.dim() == 2 else -1
+        if x0 is None:
+            x0 = torch.empty((max(B, 0), FFN_OUT), dtype=torch.float64, device=market.device)
+        want = [(market, torch.float64, (B, ffn.M)), (spots, torch.float64, (B,)),
+                (x0, torch.float64, (B, FFN_OUT))]
+        if raw is not None:
+            want.append((raw, torch.float32, (B, FFN_OUT)))
+        for t, dt, shape in want:
+            if (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda
+                    or t.device.index != self.device):
+                raise ValueError(f"ffn_forward_dev: contiguous tensors on cuda:{self.device}: "
+                                 f"market float64 [B, {ffn.M}], spots float64 [B], x0 float64 "
+                                 f"[B, {FFN_OUT}], raw float32 [B, {FFN_OUT}]")
+        st = _stream_handle("ffn_forward_dev", stream)
+        _check(load().dh_ffn_forward_dev(ffn.handle, market.data_ptr(), spots.data_ptr(), B,
+                                         x0.data_ptr(), None if raw is None else raw.data_ptr(),
+                                         _addr(st)))
+        return x0
+
     def cf(self, params16, u, tau):
         p = _f64(params16).reshape(PARAM_STRIDE)
         u = _f64(u).reshape(-1)
@@ -862,6 +909,66 @@ def iv_rows(M, mkt_iv, weights):
             f"{' ...' if len(wrong) > 8 else ''} (price outside its no-arbitrage bounds, or a "
             "non-finite vol); give them iv_weights of 0")
     return iv, w
+
+
+class FFN(_Handle):
+    """The warm-start network resident on a context's device (dh_ffn): widths = (F, hidden ...,
+    13), weights / biases the layers' float32 W_l [out, in] and b_l [out] with BatchNorm folded
+    in, C the float64 feature matrix [F, M], and the four standardisation vectors."""
+
+    def __init__(self, ctx: Context, widths, weights, biases, C_mat, x_mean, x_std, y_mean, y_std):
+        self.ctx = ctx
+        widths = np.ascontiguousarray(widths, dtype=np.int32).reshape(-1)
+        n_layers = widths.size - 1
+        if len(weights) != n_layers or len(biases) != n_layers:
+            raise ValueError("one weight matrix and one bias per layer")
+        ws, bs = [], []
+        for l, (w, b) in enumerate(zip(weights, biases)):
+            w, b = np.asarray(w), np.asarray(b)
+            if (w.dtype != np.float32 or b.dtype != np.float32
+                    or w.shape != (widths[l + 1], widths[l]) or b.shape != (widths[l + 1],)):
+                raise ValueError(f"layer {l}: float32 W [{widths[l + 1]}, {widths[l]}] and b "
+                                 f"[{widths[l + 1]}], got {w.dtype} {w.shape}, {b.dtype} {b.shape}")
+            ws.append(np.ascontiguousarray(w).reshape(-1))
+            bs.append(np.ascontiguousarray(b))
+        w_all, b_all = np.concatenate(ws), np.concatenate(bs)
+        C_mat = _f64(C_mat)
+        if C_mat.ndim != 2 or C_mat.shape[0] != widths[0]:
+            raise ValueError(f"C must be [{widths[0]}, M], got {C_mat.shape}")
+        self.F, self.M = int(C_mat.shape[0]), int(C_mat.shape[1])
+        stats = [_f64(a).reshape(-1) for a in (x_mean, x_std, y_mean, y_std)]
+        if [a.size for a in stats] != [self.F, self.F, FFN_OUT, FFN_OUT]:
+            raise ValueError(f"x_mean, x_std must be [{self.F}], y_mean, y_std [{FFN_OUT}]")
+        h = _vp()
+        with ctx._lock:
+            _check(load().dh_ffn_create(ctx.handle, n_layers, _ptr(widths, _i32p),
+                                        _ptr(w_all, _f32p), _ptr(b_all, _f32p), _ptr(C_mat),
+                                        self.M, *(_ptr(a) for a in stats), C.byref(h)))
+        self._h = h
+        # the context destroys what lives on it: Context.close() closes this object first
+        ctx.__dict__.setdefault("_ffns", []).append(weakref.ref(self))
+
+    def close(self):
+        if self._h:
+            load().dh_ffn_destroy(self._h)
+            self._h = None
+
+    def forward(self, market, spots, want_raw=False):
+        """dh_ffn_forward: market [B, M], spots [B] -> x0 float64 [B, 13], and the network's
+        standardised float32 output [B, 13] with ``want_raw``."""
+        market = _f64(market)
+        if market.ndim != 2 or market.shape[1] != self.M:
+            raise ValueError(f"market must be [B, {self.M}], got {market.shape}")
+        B = market.shape[0]
+        spots = _f64(spots).reshape(-1)
+        if spots.size != B:
+            raise ValueError("market and spots differ in length")
+        x0 = np.empty((B, FFN_OUT))
+        raw = np.empty((B, FFN_OUT), dtype=np.float32) if want_raw else None
+        with self.ctx._lock:
+            _check(load().dh_ffn_forward(self._h, _addr(market, B), _addr(spots, B), B,
+                                         _addr(x0, B), _addr(raw, B)))
+        return (x0, raw) if want_raw else x0
 
 
 class Surface(_Handle):
@@ -1849,7 +1956,7 @@ def default_context(device: int | None = None) -> Context:
 
 
 # every public top-level name, in SIGNATURES' groups: the library, context and surfaces, L-BFGS-B,
-# generator, communicator, Monte Carlo, least-squares Monte Carlo
+# generator, communicator, Monte Carlo, least-squares Monte Carlo, the warm-start network
 __all__ = [
     "LIB_PATH", "SIGNATURES", "NativeError", "load", "runtime_shared_with_torch", "device_count",
     "resolve_device", "default_context", "PARAM_STRIDE", "MAX_N", "MAX_N_PER_TERM",
@@ -1864,4 +1971,5 @@ __all__ = [
     "McOption", "MC_KINDS", "MC_MAX_OPTIONS", "MC_POISSON_CAP",
     "MC_VR_ANTITHETIC", "MC_VR_CONTROL", "MC_VR_COS_N", "MC_VR_COS_L",
     "LsmOption", "LSM_MAX_OPTIONS", "LSM_BASIS", "LSM_MIN_ITM", "LSM_SLOTS", "LSM_MAX_GIB",
+    "FFN", "FFN_OUT", "FFN_TM", "FFN_MAX_HIDDEN", "FFN_MAX_WIDTH", "FFN_MAX_IN",
 ]

@@ -32,6 +32,7 @@ from scipy.optimize._lbfgsb_py import status_messages, task_messages
 from . import _native
 from .calibrator import (_MAXFUN, N_PARAMS, PARAM_NAMES, CalibrationResult,
                          DoubleHestonJumpCalibrator, x_to_model)
+from .ffn import FFNModel
 from .generator import MATURITIES, STRIKES_PCT, grid_surface
 from .pricer import implied_vol, resolve_call
 
@@ -361,6 +362,21 @@ def default_starts(mkt, sp, r, Kabs, T, flags, multi_start):
     return out
 
 
+def check_model_grid(model, strikes_pct, maturities, strikes, flags):
+    """ValueError unless the call's option grid is the one the network's price row stands for:
+    calls on model.grid = (strikes_pct, maturities), strikes in percent of spot.  A model without
+    a stored grid (grid None) is taken at its word: the grid is then the caller's promise."""
+    if model.grid is None:
+        return
+    k, t = model.grid
+    same = (strikes is None and bool(np.all(flags))
+            and np.array_equal(np.asarray(strikes_pct, dtype=np.float64).reshape(-1), k)
+            and np.array_equal(np.asarray(maturities, dtype=np.float64).reshape(-1), t))
+    if not same:
+        raise ValueError("x0s=model: the network was trained on calls at strikes_pct "
+                         f"{k.tolist()} x maturities {t.tolist()}; this call's grid differs")
+
+
 def resolve_starts(x0s, B):
     """x0s as [B, S, 13] unconstrained: an array of that shape, or [B][S] dicts of the 13 model
     parameters (an FFN's output), mapped as inverse_transform_params maps them."""
@@ -461,9 +477,13 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
     market_prices [B, M] in grid order (maturity outer, strike inner -- the generator's), spots
     [B], risk_free a scalar or [B].  The grid is strikes_pct x maturities (strikes in percent of
     each market's spot), or strikes x maturities (absolute, the same for every market).
-    x0s: [B, S, 13] unconstrained start points, [B][S] dicts of the 13 model parameters, or None
-    for each market's start_points(multi_start) (the global RNG is consumed as a loop of
-    calibrate() calls over the markets would consume it).
+    x0s: [B, S, 13] unconstrained start points, [B][S] dicts of the 13 model parameters, an
+    FFNModel (one start per market, [B, 1, 13], from ``model.predict`` on the device: the hybrid
+    scheme is this call with maxiter=10; the global RNG is not consumed; a model that carries its
+    grid refuses another one with ValueError, for a model without one -- ``model.grid`` None --
+    the grid is the caller's promise), or None for each
+    market's start_points(multi_start) (the global RNG is consumed as a loop of calibrate() calls
+    over the markets would consume it).
 
     objective="price" (the default) fits relative price errors, the reference's loss.
     objective="iv" fits Black-Scholes vols: market_ivs [B, M] (default: the device inversion of
@@ -524,6 +544,10 @@ def calibrate_batch(market_prices, spots, risk_free, *, strikes_pct=STRIKES_PCT,
         if int(multi_start) < 0:
             raise ValueError("multi_start < 0")
         X = default_starts(mkt, sp, r, Kabs, T, flags, multi_start)
+    elif isinstance(x0s, FFNModel):
+        # one start per market from the network's device forward; no RNG draw
+        check_model_grid(x0s, strikes_pct, maturities, strikes, flags)
+        X = np.ascontiguousarray(x0s.predict(mkt, sp, device)[:, None, :])
     else:
         X = resolve_starts(x0s, B)
     S = X.shape[1]
