@@ -32,7 +32,8 @@
 //
 // param_grad_kernel, one block per (param set, tile of <= 256 options of one maturity), is the
 // Greeks kernel's shape:
-//   1. the block fills LDS with Re(w_k) and the thirteen Re(w_k D_p(u_k)) (halved at k = 0) on the
+//   1. the block fills LDS with Re(w_k) and the thirteen Re(w_k D_p(u_k)) (halved at k = 0, where
+//      the thirteen are exactly 0: phi(0) = 1) on the
 //      tile's unclamped range [a0, b0], and with 1 / (1 + u_k^2) and 1 / u_k, one lane per term:
 //      sixteen doubles per term, 128 KB at N = 1024;
 //   2. every option whose own range is [a0, b0] runs one pass over k on kLanes lanes into fourteen
@@ -216,8 +217,13 @@ __device__ __forceinline__ void cf_eval_g(const GConsts& G, double u, double a,
     const cplx Dv[kPlanes - 1] = {d1.B, d1.kap, d1.th, d1.sig, d1.rho, d2.B, d2.kap, d2.th, d2.sig,
                                   d2.rho, dlam, dmu, dsj};
     t[0] = wr;
+    // phi(0) = 1 whatever the parameters, so every D_p(0) is exactly 0.  Formed in fp64 it is a
+    // residue of the primitives' roundings instead (bm = kappa - sqrt(kappa^2), log(|D|^2 / 4 |d|^2)
+    // at 1: up to 1e-15 times c' on the sigma plane), which at N = 1 is the whole plane.  Term 0
+    // (u == 0 only there) carries the exact value.
+    const bool k0 = u == 0.0;
 #pragma unroll
-    for (int i = 0; i < kPlanes - 1; ++i) t[1 + i] = wr * Dv[i].re - wi * Dv[i].im;
+    for (int i = 0; i < kPlanes - 1; ++i) t[1 + i] = k0 ? 0.0 : wr * Dv[i].re - wi * Dv[i].im;
 }
 
 struct GradArgs {
