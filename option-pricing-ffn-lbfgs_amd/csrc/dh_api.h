@@ -789,17 +789,14 @@ void fg_points(const double* x0, const double* model, int S, double S0, double r
                 pb[i] = model[(size_t)st * kN + i];
                 pp[i] = model[((size_t)S + st) * kN + i];
             } else {
-                const bool th = i == 4 || i == 9, id = i == 11;
-                pb[i] = th ? std::tanh(x[i]) : (id ? x[i] : std::exp(x[i]));
-                pp[i] = th ? std::tanh(xh) : (id ? xh : std::exp(xh));
+                pb[i] = lb_transform(i, x[i]);
+                pp[i] = lb_transform(i, xh);
             }
         }
         for (int t = 0; t < kP; ++t) {
             double* o = rec + ((size_t)st * kP + t) * DH_PARAM_STRIDE;
             for (int i = 0; i < kN; ++i) o[i] = (i == t - 1) ? pp[i] : pb[i];
-            const double v1 = o[3] * o[3] - 2.0 * o[1] * o[2];
-            const double v2 = o[8] * o[8] - 2.0 * o[6] * o[7];
-            pen[(size_t)st * kP + t] = 1000.0 * ((v1 > 0.0 ? v1 : 0.0) + (v2 > 0.0 ? v2 : 0.0));
+            pen[(size_t)st * kP + t] = feller_penalty(o);
             o[13] = S0;
             o[14] = r;
             o[15] = 0.0;

@@ -4,10 +4,11 @@
 //     f, g, n_bad   dh_surface_loss_grad_rows's, bit for bit, and
 //     H_ij = (2 / M) dt_i dt_j sum_m a_im a_jm,   a_im = plane_i[m] / mkt_m,
 // the Gauss-Newton Hessian of the price part of the loss in the optimiser's x (dt: the transform's
-// derivative, loss_grad_wave's).  The Feller penalty enters g only.  Included by dh_kernels.hip
-// after dh_param_grad.h and ahead of dh_lb_driver.h, whose Levenberg-Marquardt iteration launches
-// it; needs dh_param_grad.h (loss_grad_wave, launch_param_grad, x_records_rows_kernel) and
-// dh_loss_rows.h (check_rows).
+// derivative, dh_kernels.hip's transform_dt).  The Feller penalty enters g only.  Included by
+// dh_kernels.hip after dh_param_grad.h and ahead of dh_lb_driver.h, whose Levenberg-Marquardt
+// iteration launches it; needs dh_param_grad.h: loss_grad_wave, launch_param_grad and the analytic
+// rows request (GradRows, rows_request_dev, rows_round_trip), which carry everything here but the
+// kernel and its launch.
 //
 // Shape.  One block of five waves per set.  Wave 0 IS loss_grad_wave<true>: the same function, so
 // the same f, g and n_bad.  Waves 1..4 own entries 23 (w - 1) .. 23 w - 1 of the 91 upper entries
@@ -106,8 +107,7 @@ __device__ __forceinline__ void hess_wave(const double* __restrict__ planes,
     const double* q = rec + s * DH_PARAM_STRIDE;
     double dt[kN];
 #pragma unroll
-    for (int i = 0; i < kN; ++i)
-        dt[i] = (i == 4 || i == 9) ? 1.0 - q[i] * q[i] : (i == 11 ? 1.0 : q[i]);
+    for (int i = 0; i < kN; ++i) dt[i] = transform_dt(i, q);
     store_entries<E0>(H + s * (kN * kN), acc, dt, 2.0 / (double)M, bad > 0, seq);
 }
 
@@ -135,33 +135,17 @@ __global__ __launch_bounds__(kBlock) void gauss_newton_rows_kernel(
     }
 }
 
-// Stages 2 and 3 of a request over records already on the device: param_grad_kernel into d_planes
-// [14][S][M], then the reduction.  The Levenberg-Marquardt driver's iteration.
-int gauss_newton_rows_launch(dh_ctx* ctx, const dh_surface* s, const double* d_rec,
-                             const double* d_pen, const double* d_mkt, const int* d_row, int S,
-                             int N, double L, double* d_planes, double* d_f, double* d_g,
-                             int* d_bad, double* d_H, hipStream_t st, const int* live_count) {
-    const int rc = dhpg::launch_param_grad(ctx, dhpg::surface_args(s, d_rec, S, N, L, d_planes), S, st);
+// Stages 2 and 3 of a request over records already on the device: param_grad_kernel into the
+// planes, then the reduction (R.extra: the Hessians).  The Levenberg-Marquardt driver's iteration.
+int gauss_newton_rows_launch(dh_ctx* ctx, const dh_surface* s, const dhpg::GradRows& R, int N,
+                             double L, hipStream_t st) {
+    const int rc =
+        dhpg::launch_param_grad(ctx, dhpg::surface_args(s, R.rec, R.S, N, L, R.planes), R.S, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(gauss_newton_rows_kernel, dim3((unsigned)S), dim3(kBlock), 0, st,
-                       (const double*)d_planes, d_rec, d_pen, d_mkt, d_row, (const int*)s->perm,
-                       s->M, (int64_t)S, live_count, d_f, d_g, d_bad, d_H);
+    hipLaunchKernelGGL(gauss_newton_rows_kernel, dim3((unsigned)R.S), dim3(kBlock), 0, st,
+                       (const double*)R.planes, R.rec, R.pen, R.mkt, R.row, (const int*)s->perm,
+                       s->M, (int64_t)R.S, R.live_count, R.f, R.g, R.bad, R.extra);
     HIP_TRY(hipGetLastError());
-    return DH_OK;
-}
-
-// dh_surface_loss_grad_rows_dev's pointer checks, and H
-int check_pointers(const void* x, const void* mkt, const void* spot, const void* rate,
-                   const void* row, const void* f, const void* g, const void* bad, const void* H) {
-    if (!x) return fail(DH_E_ARG, "x is null");
-    if (!mkt) return fail(DH_E_ARG, "mkt is null");
-    if (!spot) return fail(DH_E_ARG, "spot is null");
-    if (!rate) return fail(DH_E_ARG, "rate is null");
-    if (!row) return fail(DH_E_ARG, "row is null");
-    if (!f) return fail(DH_E_ARG, "f is null");
-    if (!g) return fail(DH_E_ARG, "g is null");
-    if (!bad) return fail(DH_E_ARG, "bad is null");
-    if (!H) return fail(DH_E_ARG, "H is null");
     return DH_OK;
 }
 
@@ -172,23 +156,20 @@ extern "C" int dh_surface_gauss_newton_rows_dev(dh_ctx* ctx, const dh_surface* s
                                                 const double* d_rate, const int32_t* d_row, int S,
                                                 int N, double L, double* d_f, double* d_g,
                                                 int32_t* d_bad, double* d_H, void* stream) {
-    int rc = dhpg::check_loss_grad_rows(ctx, s, S, N, L);
-    if (rc) return rc;
-    rc = dhgn::check_pointers(d_x, d_mkt, d_spot, d_rate, d_row, d_f, d_g, d_bad, d_H);
-    if (rc) return rc;
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    // dh_surface_loss_grad_rows_dev's scratch and layout: records, penalties, planes
-    HIP_TRY(ctx->pg_scratch.reserve(dhpg::loss_grad_scratch(S, s->M)));
-    double* d_rec = (double*)ctx->pg_scratch.ptr;
-    double* d_pen = d_rec + (size_t)S * DH_PARAM_STRIDE;
-    double* d_planes = d_pen + S;
-    hipLaunchKernelGGL(dhpg::x_records_rows_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256),
-                       0, st, d_x, S, d_spot, d_rate, (const int*)d_row, d_rec, d_pen);
-    HIP_TRY(hipGetLastError());
-    return dhgn::gauss_newton_rows_launch(ctx, s, d_rec, d_pen, d_mkt, (const int*)d_row, S, N, L,
-                                          d_planes, d_f, d_g, (int*)d_bad, d_H, st, nullptr);
+    dhpg::GradRows R{};
+    R.extra = d_H;                                   // the caller's: the scratch holds none
+    R.mkt = d_mkt;
+    R.row = (const int*)d_row;
+    R.f = d_f;
+    R.g = d_g;
+    R.bad = (int*)d_bad;
+    R.S = S;
+    return dhpg::rows_request_dev(ctx, s,
+                                  {{d_x, "x"}, {d_mkt, "mkt"}, {d_spot, "spot"}, {d_rate, "rate"},
+                                   {d_row, "row"}, {d_f, "f"}, {d_g, "g"}, {d_bad, "bad"},
+                                   {d_H, "H"}},
+                                  d_x, d_spot, d_rate, R, dhpg::Scratch::kPrice,
+                                  dhgn::gauss_newton_rows_launch, N, L, stream);
 }
 
 extern "C" int dh_surface_gauss_newton_rows(dh_ctx* ctx, const dh_surface* s, const double* x,
@@ -196,47 +177,15 @@ extern "C" int dh_surface_gauss_newton_rows(dh_ctx* ctx, const dh_surface* s, co
                                             const double* rate, const int32_t* row, int S, int B,
                                             int N, double L, double* f, double* g, int32_t* bad,
                                             double* H) {
-    int rc = dhpg::check_loss_grad_rows(ctx, s, S, N, L);
-    if (rc) return rc;
-    rc = dhgn::check_pointers(x, mkt, spot, rate, row, f, g, bad, H);
-    if (rc) return rc;
-    rc = check_rows(row, S, B);
-    if (rc) return rc;
-    for (int b = 0; b < B; ++b) {
-        if (!std::isfinite(spot[b]) || !(spot[b] > 0.0))
-            return fail(DH_E_ARG, "spot " + std::to_string(b) + " is not finite or not > 0");
-        if (!std::isfinite(rate[b]))
-            return fail(DH_E_ARG, "rate " + std::to_string(b) + " is not finite");
-    }
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    constexpr int kN = dhgn::kN;
-    const size_t xb = (size_t)S * kN * 8, hb = (size_t)S * kN * kN * 8, mb = (size_t)B * s->M * 8;
-    hipStream_t st = ctx->stream;
-    // x [S][13], then f [S], g [S][13], H [S][13][13], spot [B], rate [B], bad [S]
-    HIP_TRY(ctx->pg_io.reserve(2 * xb + hb + (size_t)S * 16 + (size_t)B * 16));
-    HIP_TRY(ctx->rows_mkt.reserve(mb));
-    HIP_TRY(ctx->rows_row.reserve((size_t)S * 4));
-    double* d_x = (double*)ctx->pg_io.ptr;
-    double* d_f = d_x + (size_t)S * kN;
-    double* d_g = d_f + S;
-    double* d_H = d_g + (size_t)S * kN;
-    double* d_spot = d_H + (size_t)S * kN * kN;
-    double* d_rate = d_spot + B;
-    int32_t* d_bad = (int32_t*)(d_rate + B);
-    HIP_TRY(hipMemcpyAsync(d_x, x, xb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_spot, spot, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_rate, rate, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->rows_mkt.ptr, mkt, mb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->rows_row.ptr, row, (size_t)S * 4, hipMemcpyHostToDevice, st));
-    rc = dh_surface_gauss_newton_rows_dev(ctx, s, d_x, (const double*)ctx->rows_mkt.ptr, d_spot,
-                                          d_rate, (const int32_t*)ctx->rows_row.ptr, S, N, L, d_f,
-                                          d_g, d_bad, d_H, st);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f, d_f, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(g, d_g, xb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(H, d_H, hb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(bad, d_bad, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DH_OK;
+    return dhpg::rows_round_trip(
+        ctx, s,
+        {{x, "x"}, {mkt, "mkt"}, {spot, "spot"}, {rate, "rate"}, {row, "row"}, {f, "f"}, {g, "g"},
+         {bad, "bad"}, {H, "H"}},
+        dhpg::RowsIo{x, mkt, nullptr, nullptr, spot, rate, row, f, g, bad, H}, S, B,
+        (size_t)S * dhgn::kN * dhgn::kN, N, L, dhpg::no_prep,
+        [&](const dhpg::RowsIo& d, hipStream_t st) {
+            return dh_surface_gauss_newton_rows_dev(ctx, s, d.x, d.mkt, d.spot, d.rate, d.row, S,
+                                                    N, L, d.f, d.g, d.bad, d.extra, st);
+        });
 }
+

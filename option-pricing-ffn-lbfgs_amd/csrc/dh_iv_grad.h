@@ -2,7 +2,10 @@
 // (dh_surface_iv_grad_rows_dev, dh_surface_loss_iv_grad_rows*; the reduction of
 // dh_calibrate_lbfgs_batch_iv_grad).  Included by dh_kernels.hip after
 // dh_param_grad.h and ahead of the L-BFGS-B driver (dh_lb_driver.h); needs dh_iv.h, dh_iv_loss.h
-// (vol_term), dh_loss_rows.h (rows_grid) and dh_param_grad.h (the planes, x_records_rows_kernel).
+// (vol_term, iv_check_weights), dh_loss_rows.h (rows_grid) and dh_param_grad.h: the planes and the
+// analytic rows request (GradRows, rows_request_dev, rows_round_trip).  What is the vol objective's
+// own stays here: the vega, the reduction kernel, its launches and the host form's weights and
+// divisors.
 //
 // Definition.  The vol objective of dh_loss_rows.h, f = sum_m w_m (v_m - mkt_iv_m)^2 / sum(w) +
 // Feller, v_m the Black-Scholes vol of the model price P_m.  v_m is defined by BS(v_m) = P_m, so
@@ -44,7 +47,7 @@ __device__ __noinline__ double vega(double v, double S0, double K, double T, dou
 // ---- the reduction ---------------------------------------------------------------------------------
 // One wave per set, dhivr::iv_sse_rows_kernel's layout and rules (by its own text, dhivl::vol_term:
 // bad prices, the clamp at the lower bound, a zero weight enters nothing, iv as used) and
-// dhpg::loss_grad_wave's gradient sums and lane-0 expressions.
+// dhpg::loss_grad_wave's gradient sums and lane-0 end (transform_dt, feller_kink_grad).
 //
 // Pass 1, every lane every pass (implied_vol's loop is wave-wide): lane l takes the surface's sorted
 // options l, l + 64, ... from 0.0; a used option adds w (d d) to sse, uncontracted, and writes
@@ -138,60 +141,34 @@ __global__ __launch_bounds__(kBlockRows, DH_IV_WAVES) void iv_grad_rows_kernel(
     const double dv = div[div_by_row ? b : s];
     f[s] = acc / dv + pen[s];
     const double c2 = 2.0 / dv;
-    // dhpg::loss_grad_wave's transform and Feller expressions
 #pragma unroll
     for (int k = 0; k < kN; ++k) {
-        const double dt = (k == 4 || k == 9) ? 1.0 - rec[k] * rec[k] : (k == 11 ? 1.0 : rec[k]);
+        const double dt = transform_dt(k, rec);
         go[k] = c2 * gs[k] * dt;
     }
-#pragma unroll
-    for (int fct = 0; fct < 2; ++fct) {
-        const int o = 5 * fct;
-        const double kap = rec[o + 1], th = rec[o + 2], sig = rec[o + 3];
-        if (sig * sig - 2.0 * kap * th > 0.0) {
-            go[o + 3] = go[o + 3] + 2000.0 * (sig * sig);
-            go[o + 1] = go[o + 1] - 2000.0 * (kap * th);
-            go[o + 2] = go[o + 2] - 2000.0 * (kap * th);
-        }
-    }
+    feller_kink_grad(rec, go);
 }
 
 // the reduction's launch: behind dh_surface_iv_grad_rows_dev, stage 3 of a rows request and the
-// vol-space analytic driver's iterations.  d_cm: [S][M] scratch.
-int iv_grad_rows_launch(const dh_surface* s, const double* d_planes, const double* d_rec,
-                        const double* d_pen, const double* d_mkt_iv, const double* d_wgt,
-                        const int* d_row, const double* d_div, bool div_by_row, int S,
-                        double* d_cm, double* d_f, double* d_g, double* d_sse, int* d_bad,
-                        double* d_iv, hipStream_t st, const int* live_count) {
-    hipLaunchKernelGGL(iv_grad_rows_kernel, dim3(rows_grid(S)), dim3(kBlockRows), 0, st, d_planes,
-                       d_rec, d_pen, (const double*)s->K, (const double*)s->T,
-                       (const int8_t*)s->call, (const int*)s->perm, d_mkt_iv, d_wgt, d_row, d_div,
-                       div_by_row ? 1 : 0, s->strike_mode, s->M, (int64_t)S, live_count, d_cm,
-                       d_iv, d_f, d_g, d_sse, d_bad);
+// vol-space analytic driver's iterations.  R.extra: the c_m plane [S][M].
+int iv_grad_rows_launch(const dh_surface* s, const dhpg::GradRows& R, hipStream_t st) {
+    hipLaunchKernelGGL(iv_grad_rows_kernel, dim3(rows_grid(R.S)), dim3(kBlockRows), 0, st,
+                       (const double*)R.planes, R.rec, R.pen, (const double*)s->K,
+                       (const double*)s->T, (const int8_t*)s->call, (const int*)s->perm, R.mkt, R.wgt, R.row, R.div, R.div_by_row ? 1 : 0,
+                       s->strike_mode, s->M, (int64_t)R.S, R.live_count, R.extra, R.iv, R.f, R.g,
+                       R.sse, R.bad);
     HIP_TRY(hipGetLastError());
     return DH_OK;
 }
 
 // Stages 2 and 3 of a rows request over records already on the device: param_grad_kernel,
-// unchanged, into d_planes [14][S][M], then the reduction.  The vol-space analytic driver's
-// iteration.
-int loss_iv_grad_rows_launch(dh_ctx* ctx, const dh_surface* s, const double* d_rec,
-                             const double* d_pen, const double* d_mkt_iv, const double* d_wgt,
-                             const int* d_row, const double* d_div, bool div_by_row, int S, int N,
-                             double L, double* d_planes, double* d_cm, double* d_f, double* d_g,
-                             int* d_bad, double* d_iv, hipStream_t st, const int* live_count) {
+// unchanged, into the planes, then the reduction.  The vol-space analytic driver's iteration.
+int loss_iv_grad_rows_launch(dh_ctx* ctx, const dh_surface* s, const dhpg::GradRows& R, int N,
+                             double L, hipStream_t st) {
     const int rc =
-        dhpg::launch_param_grad(ctx, dhpg::surface_args(s, d_rec, S, N, L, d_planes), S, st);
+        dhpg::launch_param_grad(ctx, dhpg::surface_args(s, R.rec, R.S, N, L, R.planes), R.S, st);
     if (rc) return rc;
-    return iv_grad_rows_launch(s, d_planes, d_rec, d_pen, d_mkt_iv, d_wgt, d_row, d_div,
-                               div_by_row, S, d_cm, d_f, d_g, nullptr, d_bad, d_iv, st,
-                               live_count);
-}
-
-// scratch of a request in the context's buffer: dhpg::loss_grad_scratch's records, penalties and
-// planes, then the c_m plane [S][M]
-size_t scratch_bytes(int S, int M) {
-    return dhpg::loss_grad_scratch(S, M) + (size_t)S * M * 8;
+    return iv_grad_rows_launch(s, R, st);
 }
 
 }  // namespace dhivg
@@ -215,10 +192,22 @@ extern "C" int dh_surface_iv_grad_rows_dev(dh_ctx* ctx, const dh_surface* s,
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     // the c_m plane alone (the planes are the caller's); grow-only
     HIP_TRY(ctx->pg_scratch.reserve((size_t)S * s->M * 8));
-    return dhivg::iv_grad_rows_launch(s, d_planes, d_params, d_pen, d_mkt_iv, d_wgt,
-                                      (const int*)d_row, d_div, false, S,
-                                      (double*)ctx->pg_scratch.ptr, d_f, d_g, d_sse,
-                                      (int*)d_n_bad, d_iv, st, nullptr);
+    dhpg::GradRows R{};
+    R.rec = d_params;
+    R.pen = d_pen;
+    R.planes = const_cast<double*>(d_planes);        // the caller's: this launch only reads them
+    R.extra = (double*)ctx->pg_scratch.ptr;
+    R.mkt = d_mkt_iv;
+    R.wgt = d_wgt;
+    R.row = (const int*)d_row;
+    R.div = d_div;
+    R.f = d_f;
+    R.g = d_g;
+    R.sse = d_sse;
+    R.bad = (int*)d_n_bad;
+    R.iv = d_iv;
+    R.S = S;
+    return dhivg::iv_grad_rows_launch(s, R, st);
 }
 
 extern "C" int dh_surface_loss_iv_grad_rows_dev(dh_ctx* ctx, const dh_surface* s,
@@ -228,33 +217,21 @@ extern "C" int dh_surface_loss_iv_grad_rows_dev(dh_ctx* ctx, const dh_surface* s
                                                 const int32_t* d_row, int S, int N, double L,
                                                 double* d_f, double* d_g, int32_t* d_bad,
                                                 double* d_iv, void* stream) {
-    int rc = dhpg::check_loss_grad_rows(ctx, s, S, N, L);
-    if (rc) return rc;
-    if (!d_x) return fail(DH_E_ARG, "x is null");
-    if (!d_mkt_iv) return fail(DH_E_ARG, "mkt_iv is null");
-    if (!d_wgt) return fail(DH_E_ARG, "wgt is null");
-    if (!d_div) return fail(DH_E_ARG, "div is null");
-    if (!d_spot) return fail(DH_E_ARG, "spot is null");
-    if (!d_rate) return fail(DH_E_ARG, "rate is null");
-    if (!d_row) return fail(DH_E_ARG, "row is null");
-    if (!d_f) return fail(DH_E_ARG, "f is null");
-    if (!d_g) return fail(DH_E_ARG, "g is null");
-    if (!d_bad) return fail(DH_E_ARG, "bad is null");
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    // dh_surface_loss_grad_rows_dev's scratch and layout, then the c_m plane
-    HIP_TRY(ctx->pg_scratch.reserve(dhivg::scratch_bytes(S, s->M)));
-    double* d_rec = (double*)ctx->pg_scratch.ptr;
-    double* d_pen = d_rec + (size_t)S * DH_PARAM_STRIDE;
-    double* d_planes = d_pen + S;
-    double* d_cm = d_planes + (size_t)dhpg::kPlanes * S * s->M;
-    hipLaunchKernelGGL(dhpg::x_records_rows_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256),
-                       0, st, d_x, S, d_spot, d_rate, (const int*)d_row, d_rec, d_pen);
-    HIP_TRY(hipGetLastError());
-    return dhivg::loss_iv_grad_rows_launch(ctx, s, d_rec, d_pen, d_mkt_iv, d_wgt,
-                                           (const int*)d_row, d_div, false, S, N, L, d_planes,
-                                           d_cm, d_f, d_g, (int*)d_bad, d_iv, st, nullptr);
+    dhpg::GradRows R{};
+    R.mkt = d_mkt_iv;
+    R.wgt = d_wgt;
+    R.row = (const int*)d_row;
+    R.div = d_div;
+    R.f = d_f;
+    R.g = d_g;
+    R.bad = (int*)d_bad;
+    R.iv = d_iv;
+    R.S = S;
+    return dhpg::rows_request_dev(
+        ctx, s,
+        {{d_x, "x"}, {d_mkt_iv, "mkt_iv"}, {d_wgt, "wgt"}, {d_div, "div"}, {d_spot, "spot"},
+         {d_rate, "rate"}, {d_row, "row"}, {d_f, "f"}, {d_g, "g"}, {d_bad, "bad"}},
+        d_x, d_spot, d_rate, R, dhpg::Scratch::kVol, dhivg::loss_iv_grad_rows_launch, N, L, stream);
 }
 
 extern "C" int dh_surface_loss_iv_grad_rows(dh_ctx* ctx, const dh_surface* s, const double* x,
@@ -262,67 +239,25 @@ extern "C" int dh_surface_loss_iv_grad_rows(dh_ctx* ctx, const dh_surface* s, co
                                             const double* spot, const double* rate,
                                             const int32_t* row, int S, int B, int N, double L,
                                             double* f, double* g, int32_t* bad, double* iv) {
-    int rc = dhpg::check_loss_grad_rows(ctx, s, S, N, L);
-    if (rc) return rc;
-    if (!x) return fail(DH_E_ARG, "x is null");
-    if (!mkt_iv) return fail(DH_E_ARG, "mkt_iv is null");
-    if (!spot) return fail(DH_E_ARG, "spot is null");
-    if (!rate) return fail(DH_E_ARG, "rate is null");
-    if (!row) return fail(DH_E_ARG, "row is null");
-    if (!f) return fail(DH_E_ARG, "f is null");
-    if (!g) return fail(DH_E_ARG, "g is null");
-    if (!bad) return fail(DH_E_ARG, "bad is null");
-    rc = check_rows(row, S, B);
-    if (rc) return rc;
-    for (int b = 0; b < B; ++b) {
-        if (!std::isfinite(spot[b]) || !(spot[b] > 0.0))
-            return fail(DH_E_ARG, "spot " + std::to_string(b) + " is not finite or not > 0");
-        if (!std::isfinite(rate[b]))
-            return fail(DH_E_ARG, "rate " + std::to_string(b) + " is not finite");
-    }
-    const int M = s->M;
     // the weights as the reduction reads them ([B][M], null: all 1), each market's weight sum
     // (dh_calibrate_lbfgs_batch_iv's checks and order) and each set's divisor
-    std::vector<double> w((size_t)B * M), wsum((size_t)B, 0.0), dv((size_t)S);
-    rc = iv_check_weights(mkt_iv, wgt, B, M, true, w.data(), wsum.data());
-    if (rc) return rc;
-    for (int i = 0; i < S; ++i) dv[i] = wsum[row[i]];
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    constexpr int kN = dhivg::kN;
-    const size_t xb = (size_t)S * kN * 8, mb = (size_t)B * M * 8, ob = (size_t)S * M * 8;
-    hipStream_t st = ctx->stream;
-    DrainOnError drain{st};                          // w, dv are pageable: drained before they go
-    // x [S][13], then f [S], g [S][13], div [S], spot [B], rate [B], bad [S]
-    HIP_TRY(ctx->pg_io.reserve(2 * xb + (size_t)S * 24 + (size_t)B * 16));
-    HIP_TRY(ctx->rows_mkt.reserve(mb));
-    HIP_TRY(ctx->rows_wgt.reserve(mb));
-    HIP_TRY(ctx->rows_row.reserve((size_t)S * 4));
-    if (iv) HIP_TRY(ctx->iv.reserve(ob));
-    double* d_x = (double*)ctx->pg_io.ptr;
-    double* d_f = d_x + (size_t)S * kN;
-    double* d_g = d_f + S;
-    double* d_div = d_g + (size_t)S * kN;
-    double* d_spot = d_div + S;
-    double* d_rate = d_spot + B;
-    int32_t* d_bad = (int32_t*)(d_rate + B);
-    HIP_TRY(hipMemcpyAsync(d_x, x, xb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_div, dv.data(), (size_t)S * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_spot, spot, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_rate, rate, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->rows_mkt.ptr, mkt_iv, mb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->rows_wgt.ptr, w.data(), mb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->rows_row.ptr, row, (size_t)S * 4, hipMemcpyHostToDevice, st));
-    rc = dh_surface_loss_iv_grad_rows_dev(ctx, s, d_x, (const double*)ctx->rows_mkt.ptr,
-                                          (const double*)ctx->rows_wgt.ptr, d_div, d_spot, d_rate,
-                                          (const int32_t*)ctx->rows_row.ptr, S, N, L, d_f, d_g,
-                                          d_bad, iv ? (double*)ctx->iv.ptr : nullptr, st);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f, d_f, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(g, d_g, xb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(bad, d_bad, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-    if (iv) HIP_TRY(hipMemcpyAsync(iv, ctx->iv.ptr, ob, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    drain.armed = false;
-    return DH_OK;
+    auto prep = [&](std::vector<double>& w, std::vector<double>& dv) -> int {
+        std::vector<double> wsum((size_t)B, 0.0);
+        w.resize((size_t)B * s->M);
+        dv.resize((size_t)S);
+        const int rc = iv_check_weights(mkt_iv, wgt, B, s->M, true, w.data(), wsum.data());
+        if (rc) return rc;
+        for (int i = 0; i < S; ++i) dv[i] = wsum[row[i]];
+        return DH_OK;
+    };
+    return dhpg::rows_round_trip(
+        ctx, s,
+        {{x, "x"}, {mkt_iv, "mkt_iv"}, {spot, "spot"}, {rate, "rate"}, {row, "row"}, {f, "f"},
+         {g, "g"}, {bad, "bad"}},
+        dhpg::RowsIo{x, mkt_iv, nullptr, nullptr, spot, rate, row, f, g, bad, iv}, S, B,
+        s ? (size_t)S * s->M : 0, N, L, prep, [&](const dhpg::RowsIo& d, hipStream_t st) {
+            return dh_surface_loss_iv_grad_rows_dev(ctx, s, d.x, d.mkt, d.wgt, d.div, d.spot,
+                                                    d.rate, d.row, S, N, L, d.f, d.g, d.bad,
+                                                    d.extra, st);
+        });
 }

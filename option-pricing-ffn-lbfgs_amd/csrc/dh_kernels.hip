@@ -2774,16 +2774,43 @@ constexpr double kInvalidLoss = 1e10;                 // lbfgs_calibrator.py:152
 constexpr double kFdStep = 1e-8;                      // SciPy L-BFGS-B eps
 constexpr double kSqrtEps = 1.4901161193847656e-08;   // sqrt(DBL_EPSILON), _numdiff fallback
 
+// ---- the record arithmetic, defined once for every optimiser path, device and host ---------------
 // model parameter i from unconstrained x_i (lbfgs_calibrator.py:62-87): tanh for the two
 // correlations, identity for mu_j, exp otherwise
-__device__ __forceinline__ double lb_transform(int i, double x) {
+__host__ __device__ __forceinline__ double lb_transform(int i, double x) {
     if (i == 4 || i == 9) return tanh(x);
     if (i == 11) return x;
     return exp(x);
 }
 
+// d lb_transform(i, x_i) / d x_i from the model parameters q
+__device__ __forceinline__ double transform_dt(int i, const double* q) {
+    return (i == 4 || i == 9) ? 1.0 - q[i] * q[i] : (i == 11 ? 1.0 : q[i]);
+}
+
+// the Feller penalty (lbfgs_calibrator.py:113-116): 1000 max(0, sigma^2 - 2 kappa theta) per factor
+__host__ __device__ __forceinline__ double feller_penalty(const double* p) {
+    const double v1 = p[3] * p[3] - 2.0 * p[1] * p[2];
+    const double v2 = p[8] * p[8] - 2.0 * p[6] * p[7];
+    return 1000.0 * ((v1 > 0.0 ? v1 : 0.0) + (v2 > 0.0 ? v2 : 0.0));
+}
+
+// adds d feller_penalty / d x to go [13], per factor where its slack is strictly positive
+__device__ __forceinline__ void feller_kink_grad(const double* q, double* go) {
+#pragma unroll
+    for (int fct = 0; fct < 2; ++fct) {
+        const int o = 5 * fct;
+        const double kap = q[o + 1], th = q[o + 2], sig = q[o + 3];
+        if (sig * sig - 2.0 * kap * th > 0.0) {
+            go[o + 3] = go[o + 3] + 2000.0 * (sig * sig);
+            go[o + 1] = go[o + 1] - 2000.0 * (kap * th);
+            go[o + 2] = go[o + 2] - 2000.0 * (kap * th);
+        }
+    }
+}
+
 // unconstrained x [S][13] -> param records (exp / tanh / identity, lbfgs_calibrator.py:62-87)
-// and Feller penalties (:113-116); one thread per set, the expressions of lb_emit
+// and Feller penalties (:113-116); one thread per set
 __global__ void x_records_kernel(const double* __restrict__ x, int S, double S0, double r,
                                  double* __restrict__ rec, double* __restrict__ pen) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2791,9 +2818,7 @@ __global__ void x_records_kernel(const double* __restrict__ x, int S, double S0,
     double p[dhlb::kN];
 #pragma unroll
     for (int i = 0; i < dhlb::kN; ++i) p[i] = lb_transform(i, x[(size_t)s * dhlb::kN + i]);
-    const double v1 = p[3] * p[3] - 2.0 * p[1] * p[2];
-    const double v2 = p[8] * p[8] - 2.0 * p[6] * p[7];
-    pen[s] = 1000.0 * ((v1 > 0.0 ? v1 : 0.0) + (v2 > 0.0 ? v2 : 0.0));
+    pen[s] = feller_penalty(p);
     double* out = rec + (size_t)s * DH_PARAM_STRIDE;
 #pragma unroll
     for (int i = 0; i < dhlb::kN; ++i) out[i] = p[i];
@@ -2828,11 +2853,11 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
                              // variates): dh_host.h, dh_api.h
 #include "dh_lsm.h"          // American / Bermudan options by least-squares Monte Carlo: dh_mc.h
 #include "dh_greeks.h"       // analytic Greeks of the COS price: dh_host.h
-#include "dh_param_grad.h"   // analytic parameter sensitivities, loss + gradient: dh_greeks.h,
-                             // dh_loss_rows.h, dh_api.h
-#include "dh_iv_grad.h"      // the vol objective's exact gradient: dh_iv_loss.h, dh_loss_rows.h,
-                             // dh_param_grad.h
-#include "dh_gauss_newton.h" // the Gauss-Newton rows reduction: dh_param_grad.h, dh_loss_rows.h
+#include "dh_param_grad.h"   // analytic parameter sensitivities, loss + gradient, and the analytic
+                             // rows request (GradRows, its scratch, epilogue and host path):
+                             // dh_greeks.h, dh_loss_rows.h, dh_api.h
+#include "dh_iv_grad.h"      // the vol objective's exact gradient: dh_iv_loss.h, dh_param_grad.h
+#include "dh_gauss_newton.h" // the Gauss-Newton rows reduction: dh_param_grad.h
 #include "dh_lb_driver.h"    // the device-resident L-BFGS-B and Levenberg-Marquardt: dh_api.h,
                              // dh_iv_loss.h, dh_loss_rows.h, dh_param_grad.h, dh_iv_grad.h,
                              // dh_gauss_newton.h

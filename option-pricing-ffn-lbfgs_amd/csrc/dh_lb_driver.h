@@ -4,8 +4,10 @@
 // its launch and the host loop; and the Levenberg-Marquardt driver on the same host loop
 // (dh_calibrate_lm_batch: lm_step_kernel around dh_lm.h's state machine).  Included by dh_kernels.hip after the loss stages (dh_iv_loss.h,
 // dh_loss_rows.h, dh_param_grad.h, dh_iv_grad.h), whose launches the host loop calls;
-// kInvalidLoss, kFdStep, kSqrtEps and lb_transform, which the one-shot entry points share, stay in
-// dh_kernels.hip.  DESIGN.md 3.8, 3.12-3.14, 3.19, 3.20.
+// kInvalidLoss, kFdStep, kSqrtEps and the record arithmetic (lb_transform, feller_penalty), which
+// the one-shot entry points share, stay in dh_kernels.hip.  The analytic iterations are one
+// dhpg::GradRows (dh_param_grad.h) built once per run over carve_grad_scratch's layout, and one of
+// the three rows launches picked once.  DESIGN.md 3.8, 3.12-3.14, 3.19-3.21, 3.23.
 //
 // Nothing here is contracted into FMAs: the step kernel must compute the bits of the CPU build
 // of dh_lbfgs.h (tests/native/lb_host.cpp).
@@ -221,9 +223,7 @@ __device__ void lb_emit(const WaveCore& c, WaveVec& dx, WaveVec& pen, double* pb
         double p[dhlb::kN];
 #pragma unroll
         for (int i = 0; i < dhlb::kN; ++i) p[i] = (i == lane - 1) ? pp[i] : pb[i];
-        const double v1 = p[3] * p[3] - 2.0 * p[1] * p[2];
-        const double v2 = p[8] * p[8] - 2.0 * p[6] * p[7];
-        pen.v = 1000.0 * ((v1 > 0.0 ? v1 : 0.0) + (v2 > 0.0 ? v2 : 0.0));
+        pen.v = feller_penalty(p);
         double* out = A.rec + ((size_t)slot * dhlb::kPts + lane) * DH_PARAM_STRIDE;
 #pragma unroll
         for (int i = 0; i < dhlb::kN; ++i) out[i] = p[i];
@@ -242,15 +242,13 @@ __device__ void lb_emit(const WaveCore& c, WaveVec& dx, WaveVec& pen, double* pb
 // The analytic-gradient driver's request (dh_calibrate_lbfgs_batch_grad, and dh_calibrate_lm_batch's):
 // the one record of xe, no bumps and no dx.  Lane i < 13 maps x_i = xi to its model param and writes it; lanes 13..15 write the
 // start's spot, its rate and q = 0; lane 0 writes the set's market row and the record's Feller
-// penalty, x_records_kernel's expression, which the rows reduction adds to the loss.
+// penalty (feller_penalty, as the record kernels'), which the rows reduction adds to the loss.
 __device__ void lb_emit_grad(double xi, WaveVec& dx, WaveVec& pen, double* pb, const LbArgs& A,
                              int slot, int lane, int sidx) {
     dx.v = 0.0;
     if (lane < dhlb::kN) pb[lane] = lb_transform(lane, xi);
     __syncthreads();
-    const double v1 = pb[3] * pb[3] - 2.0 * pb[1] * pb[2];
-    const double v2 = pb[8] * pb[8] - 2.0 * pb[6] * pb[7];
-    pen.v = 1000.0 * ((v1 > 0.0 ? v1 : 0.0) + (v2 > 0.0 ? v2 : 0.0));
+    pen.v = feller_penalty(pb);
     double* out = A.rec + (size_t)slot * DH_PARAM_STRIDE;
     if (lane < dhlb::kN) out[lane] = pb[lane];
     else if (lane == 13) out[13] = A.spot_of[sidx];
@@ -644,12 +642,8 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
         if (bt->B > 0 && (!bt->mkt || !bt->spot || !bt->rate))
             return fail(DH_E_ARG, "null argument");
         if (S > 0 && !bt->market_of) return fail(DH_E_ARG, "null argument");
-        for (int b = 0; b < bt->B; ++b) {
-            if (!std::isfinite(bt->spot[b]) || !(bt->spot[b] > 0.0))
-                return fail(DH_E_ARG, "spot " + std::to_string(b) + " is not finite or not > 0");
-            if (!std::isfinite(bt->rate[b]))
-                return fail(DH_E_ARG, "rate " + std::to_string(b) + " is not finite");
-        }
+        rc = check_spot_rate(bt->spot, bt->rate, bt->B);
+        if (rc) return rc;
         for (int i = 0; i < S; ++i)
             if (bt->market_of[i] < 0 || bt->market_of[i] >= bt->B)
                 return fail(DH_E_ARG, "market_of " + std::to_string(i) + " is outside [0, B)");
@@ -684,13 +678,12 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
         const size_t mb = (size_t)bt->B * M * 8;
         HIP_TRY(ctx->rows_mkt.reserve(mb));
         HIP_TRY(ctx->rows_row.reserve(npts * 4));
-        if (grad)   // once, for all S starts: the gradients [S][16], penalties [S], planes [14][S][M]
-                    // and under the vol objective the c_m plane [S][M] (dh_iv_grad.h)
-                    // and under Levenberg-Marquardt the Hessians [S][13][13] after the planes
-            HIP_TRY(ctx->pg_scratch.reserve(
-                bt->iv_wgt ? dhivg::scratch_bytes(S, M)
-                           : dhpg::loss_grad_scratch(S, M) +
-                                 (lm ? (size_t)S * dhlm::kN * dhlm::kN * 8 : 0)));
+        if (grad)   // once, for all S starts: a rows request's scratch, with the vol objective's
+                    // c_m plane or Levenberg-Marquardt's Hessians after the planes
+            HIP_TRY(ctx->pg_scratch.reserve(dhpg::grad_scratch_bytes(
+                S, M,
+                bt->iv_wgt ? dhpg::Scratch::kVol
+                           : (lm ? dhpg::Scratch::kHess : dhpg::Scratch::kPrice))));
         else
             HIP_TRY(ctx->lb_prices.reserve(npts * M * 8));
         HIP_TRY(ctx->lb_spot.reserve((size_t)S * 8));
@@ -771,15 +764,32 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
     const bool batch = bt != nullptr;
     const bool iv = batch && bt->iv_wgt != nullptr;
     A.div_of = iv ? (const double*)ctx->lb_div.ptr : nullptr;
-    // dh_surface_loss_grad_dev's scratch layout with the gradients where it keeps its records (the
-    // driver's records are lb_rec, one per live start)
-    double* const d_grad = grad ? (double*)ctx->pg_scratch.ptr : nullptr;
-    double* const d_pen = grad ? d_grad + (size_t)S * DH_PARAM_STRIDE : nullptr;
-    double* const d_planes = grad ? d_pen + S : nullptr;
-    double* const d_cm = grad && iv ? d_planes + (size_t)dhpg::kPlanes * S * M : nullptr;
-    double* const d_hess = lm ? d_planes + (size_t)dhpg::kPlanes * S * M : nullptr;
-    A.grad = d_grad;
-    A.pen_out = d_pen;
+    // The analytic request of an iteration, over all S starts' scratch: the one-shot calls' carve
+    // with the gradients [S][16] where they keep their records (the driver's records are lb_rec,
+    // one per live start).  The step kernel writes the records, rows and penalties and reads f
+    // (sse) and g (grad) finished; under the vol objective rows_mkt holds vols.
+    dhpg::GradRows R{};
+    dhpg::GradScratch c{};
+    dhpg::RowsLaunch rows_launch = nullptr;
+    if (grad) {
+        c = dhpg::carve_grad_scratch(ctx->pg_scratch.ptr, S, M);
+        R.rec = A.rec, R.pen = c.pen, R.planes = c.planes, R.extra = c.extra;
+        R.mkt = (const double*)ctx->rows_mkt.ptr;
+        R.wgt = iv ? (const double*)ctx->rows_wgt.ptr : nullptr;
+        R.row = A.row;
+        R.div = iv ? (const double*)ctx->lb_wsum.ptr : nullptr;
+        R.div_by_row = true;
+        R.f = (double*)A.sse;
+        R.g = c.rec;
+        R.bad = (int*)A.bad;
+        R.live_count = A.live_count;
+        rows_launch = lm   ? dhgn::gauss_newton_rows_launch
+                      : iv ? dhivg::loss_iv_grad_rows_launch
+                           : dhpg::loss_grad_rows_launch;
+    }
+    A.grad = c.rec;
+    A.pen_out = c.pen;
+    double* const d_hess = lm ? R.extra : nullptr;
     auto set_inline = [&](const int* lst, int n) {
         A.n_inline = !lm && n <= kLbInline ? 1 : 0;   // lm_step_kernel reads the list from memory
         for (int i = 0; i < kLbInline; ++i) A.live_inline[i] = i < n && A.n_inline ? lst[i] : 0;
@@ -806,28 +816,13 @@ static int lb_run(dh_ctx* ctx, const dh_surface* s, const double* x0, int S, dou
     int64_t iters = 0, launches = 0;
     auto enqueue_chunk = [&](int k) -> int {
         A.mode = 1;
+        R.S = n_live;
         for (int c = 0; c < chunk; ++c) {
             int e;
             if (grad) {
                 // the planes of the live starts' records, then each set's loss and gradient
                 // against its start's market row; the step reads them finished
-                if (lm)
-                    e = dhgn::gauss_newton_rows_launch(ctx, s, A.rec, d_pen,
-                                                       (const double*)ctx->rows_mkt.ptr, A.row,
-                                                       n_live, N, L, d_planes, (double*)A.sse,
-                                                       d_grad, (int*)A.bad, d_hess, st,
-                                                       A.live_count);
-                else if (iv)                           // rows_mkt holds vols
-                    e = dhivg::loss_iv_grad_rows_launch(
-                        ctx, s, A.rec, d_pen, (const double*)ctx->rows_mkt.ptr,
-                        (const double*)ctx->rows_wgt.ptr, A.row, (const double*)ctx->lb_wsum.ptr,
-                        true, n_live, N, L, d_planes, d_cm, (double*)A.sse, d_grad, (int*)A.bad,
-                        nullptr, st, A.live_count);
-                else
-                    e = dhpg::loss_grad_rows_launch(ctx, s, A.rec, d_pen,
-                                                    (const double*)ctx->rows_mkt.ptr, A.row,
-                                                    n_live, N, L, d_planes, (double*)A.sse, d_grad,
-                                                    (int*)A.bad, st, A.live_count);
+                e = rows_launch(ctx, s, R, N, L, st);
                 if (e) return e;
                 e = launch_step(n_live);
                 if (e) return e;

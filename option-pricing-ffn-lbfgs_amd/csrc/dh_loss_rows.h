@@ -28,6 +28,17 @@ int check_rows(const int32_t* row, int S, int B) {
     return DH_OK;
 }
 
+// the spot and rate of every market of a rows request or a batch calibration
+int check_spot_rate(const double* spot, const double* rate, int B) {
+    for (int b = 0; b < B; ++b) {
+        if (!std::isfinite(spot[b]) || !(spot[b] > 0.0))
+            return fail(DH_E_ARG, "spot " + std::to_string(b) + " is not finite or not > 0");
+        if (!std::isfinite(rate[b]))
+            return fail(DH_E_ARG, "rate " + std::to_string(b) + " is not finite");
+    }
+    return DH_OK;
+}
+
 }  // namespace
 
 // ---- relative price ---------------------------------------------------------------------------

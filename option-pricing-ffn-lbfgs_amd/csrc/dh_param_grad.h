@@ -2,8 +2,14 @@
 // the calibration loss with its exact gradient (dh_surface_param_sens*, dh_param_sens_pairs,
 // dh_surface_loss_grad*, and against a market row per set dh_surface_loss_grad_rows*; DESIGN.md
 // 3.18, 3.19).  Included by dh_kernels.hip after dh_greeks.h and ahead of the L-BFGS-B driver
-// (dh_lb_driver.h); needs the kernels' helpers (xor_sum, option_logk), dh_host.h, dh_loss_rows.h
-// and dh_api.h's x_records_kernel.
+// (dh_lb_driver.h); needs the kernels' helpers (xor_sum, option_logk), dh_kernels.hip's record
+// arithmetic (x_records_kernel, feller_penalty, transform_dt, feller_kink_grad), dh_host.h,
+// dh_iv_loss.h (DrainOnError) and dh_loss_rows.h (rows_grid, check_rows, check_spot_rate).
+//
+// The analytic rows request lives here too, once, for the three objectives that share it (the
+// price objective below, dh_iv_grad.h's vol one, dh_gauss_newton.h's Gauss-Newton reduction):
+// GradRows names a request's buffers, carve_grad_scratch alone knows the scratch layout,
+// rows_request_dev is the _dev entry points' body and rows_round_trip the host entry points'.
 //
 // Definition.  In dh_greeks.h's notation (xK = log(K / S0), [a, b] = truncationRange(L), u_k =
 // k pi / (b - a), w_k = phi(u_k) e^{-i u_k a}, price = e^{-rT} sum'_{k < N} Re(w_k) V_k), for a
@@ -51,6 +57,8 @@
 // the correlations, 1 for mu_j; the Feller term's derivative where its slack is strictly positive).
 // A set with an invalid price (NaN, +-inf or <= 0) gets f = 1e10 and g = 0.
 #pragma once
+
+#include <initializer_list>
 
 namespace dhpg {
 
@@ -472,6 +480,7 @@ int check_args(const dh_ctx* ctx, int64_t count, const char* count_name, int N, 
 // of the surface's *sorted* options l, l + 64, ... in that order (planes read at the option's place
 // in the caller's order, perm[m]); then the xor butterfly over the 64 lanes.  Nothing is contracted.
 // The order is a function of M and the surface's option sort alone.
+
 // mkt: the set's market prices, in the surface's sorted order (kCaller false: the surface's own)
 // or in the caller's option order (kCaller true: a market row, read at perm[m]).
 template <bool kCaller>
@@ -517,20 +526,10 @@ __device__ __forceinline__ void loss_grad_wave(
     const double c2 = 2.0 / (double)M;
 #pragma unroll
     for (int i = 0; i < kPlanes - 1; ++i) {
-        const double dt = (i == 4 || i == 9) ? 1.0 - q[i] * q[i] : (i == 11 ? 1.0 : q[i]);
+        const double dt = transform_dt(i, q);
         go[i] = c2 * gs[i] * dt;
     }
-    // Feller: 1000 max(0, sigma^2 - 2 kappa theta) per factor, where the slack is > 0
-#pragma unroll
-    for (int fct = 0; fct < 2; ++fct) {
-        const int o = 5 * fct;
-        const double kap = q[o + 1], th = q[o + 2], sig = q[o + 3];
-        if (sig * sig - 2.0 * kap * th > 0.0) {
-            go[o + 3] = go[o + 3] + 2000.0 * (sig * sig);
-            go[o + 1] = go[o + 1] - 2000.0 * (kap * th);
-            go[o + 2] = go[o + 2] - 2000.0 * (kap * th);
-        }
-    }
+    feller_kink_grad(q, go);
 }
 
 __global__ __launch_bounds__(kBlockRows) void loss_grad_kernel(
@@ -546,7 +545,7 @@ __global__ __launch_bounds__(kBlockRows) void loss_grad_kernel(
 // ---- the same against a market row per set (dh_surface_loss_grad_rows*, the analytic batch
 // driver's reduction) ---------------------------------------------------------------
 // x_records_kernel (dh_kernels.hip) with each set's spot and rate taken from its market row: the
-// same transform and Feller expressions, so the same records and penalties for the same inputs.
+// same x_record, so the same records and penalties for the same inputs.
 __global__ void x_records_rows_kernel(const double* __restrict__ x, int S,
                                       const double* __restrict__ spot,
                                       const double* __restrict__ rate, const int* __restrict__ row,
@@ -556,9 +555,7 @@ __global__ void x_records_rows_kernel(const double* __restrict__ x, int S,
     double p[dhlb::kN];
 #pragma unroll
     for (int i = 0; i < dhlb::kN; ++i) p[i] = lb_transform(i, x[(size_t)s * dhlb::kN + i]);
-    const double v1 = p[3] * p[3] - 2.0 * p[1] * p[2];
-    const double v2 = p[8] * p[8] - 2.0 * p[6] * p[7];
-    pen[s] = 1000.0 * ((v1 > 0.0 ? v1 : 0.0) + (v2 > 0.0 ? v2 : 0.0));
+    pen[s] = feller_penalty(p);
     double* out = rec + (size_t)s * DH_PARAM_STRIDE;
 #pragma unroll
     for (int i = 0; i < dhlb::kN; ++i) out[i] = p[i];
@@ -584,25 +581,62 @@ __global__ __launch_bounds__(kBlockRows) void loss_grad_rows_kernel(
                          n_bad);
 }
 
-// Stages 2 and 3 of a rows request over records already on the device: param_grad_kernel into
-// d_planes [14][S][M], then the rows reduction.  The analytic batch driver's iteration.
-int loss_grad_rows_launch(dh_ctx* ctx, const dh_surface* s, const double* d_rec,
-                          const double* d_pen, const double* d_mkt, const int* d_row, int S, int N,
-                          double L, double* d_planes, double* d_f, double* d_g, int* d_bad,
-                          hipStream_t st, const int* live_count) {
-    const int rc = launch_param_grad(ctx, surface_args(s, d_rec, S, N, L, d_planes), S, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(loss_grad_rows_kernel, dim3(rows_grid(S)), dim3(kBlockRows), 0, st,
-                       (const double*)d_planes, d_rec, d_pen, d_mkt, d_row, (const int*)s->perm,
-                       s->M, (int64_t)S, live_count, d_f, d_g, d_bad);
-    HIP_TRY(hipGetLastError());
-    return DH_OK;
+// ---- one analytic rows request: its buffers ---------------------------------------------------------
+// All device memory.  The three objectives' launches (loss_grad_rows_launch here,
+// dhivg::loss_iv_grad_rows_launch, dhgn::gauss_newton_rows_launch) read what they need of it.
+struct GradRows {
+    const double *rec, *pen; // scratch (carve_grad_scratch): records [S][16], Feller penalties [S],
+    double *planes, *extra;  // planes [14][S][M], then the vol c_m plane [S][M] or H [S][13][13]
+    const double *mkt, *wgt; // the markets [B][M]: prices or vols, and the vol objective's weights
+    const int* row;          // [S] each set's market
+    const double* div;       // the vol objective's loss divisor: [S], or with div_by_row [B] read
+    bool div_by_row;         // at row[s] (the driver's form: its sets move between slots)
+    double *f, *g, *sse;     // results: [S], [S][13], and [S] or null (the vol reduction alone)
+    int* bad;                // [S]
+    double* iv;              // [S][M] the vols as used, or null
+    int S;
+    const int* live_count;   // the device-resident driver's count of unfinished starts, or null
+};
+
+enum class Scratch { kPrice, kVol, kHess };     // what follows the planes: nothing, c_m, Hessians
+
+// scratch of a request in the context's buffer: records [S][16], penalties [S], planes [14][S][M],
+// then the kind's extra
+size_t grad_scratch_bytes(int S, int M, Scratch kind) {
+    const size_t extra = kind == Scratch::kVol    ? (size_t)S * M
+                         : kind == Scratch::kHess ? (size_t)S * (kPlanes - 1) * (kPlanes - 1)
+                                                  : 0;
+    return ((size_t)S * (DH_PARAM_STRIDE + 1) + (size_t)kPlanes * S * M + extra) * 8;
 }
 
-// scratch of a loss_grad request in the context's buffer: records [S][16], penalties [S], planes
-// [14][S][M]
-size_t loss_grad_scratch(int S, int M) {
-    return ((size_t)S * (DH_PARAM_STRIDE + 1) + (size_t)kPlanes * S * M) * 8;
+// the one place that knows that layout (extra: valid where grad_scratch_bytes counted one)
+struct GradScratch {
+    double *rec, *pen, *planes, *extra;
+};
+GradScratch carve_grad_scratch(void* ptr, int S, int M) {
+    GradScratch c;
+    c.rec = (double*)ptr;
+    c.pen = c.rec + (size_t)S * DH_PARAM_STRIDE;
+    c.planes = c.pen + S;
+    c.extra = c.planes + (size_t)kPlanes * S * M;
+    return c;
+}
+
+// stages 2 and 3 of a request over records already on the device
+using RowsLaunch = int (*)(dh_ctx*, const dh_surface*, const GradRows&, int N, double L,
+                           hipStream_t);
+
+// param_grad_kernel into the planes, then the rows reduction.  The analytic batch driver's
+// iteration.
+int loss_grad_rows_launch(dh_ctx* ctx, const dh_surface* s, const GradRows& R, int N, double L,
+                          hipStream_t st) {
+    const int rc = launch_param_grad(ctx, surface_args(s, R.rec, R.S, N, L, R.planes), R.S, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loss_grad_rows_kernel, dim3(rows_grid(R.S)), dim3(kBlockRows), 0, st,
+                       (const double*)R.planes, R.rec, R.pen, R.mkt, R.row, (const int*)s->perm,
+                       s->M, (int64_t)R.S, R.live_count, R.f, R.g, R.bad);
+    HIP_TRY(hipGetLastError());
+    return DH_OK;
 }
 
 int check_loss_grad(const dh_ctx* ctx, const dh_surface* s, int S, double S0, double r, int N,
@@ -625,6 +659,119 @@ int check_loss_grad_rows(const dh_ctx* ctx, const dh_surface* s, int S, int N, d
     if (s->M == 0) return fail(DH_E_ARG, "surface is empty (the loss is NaN)");
     return DH_OK;
 }
+
+// ---- one analytic rows request: its entry points ----------------------------------------------------
+// the pointers an entry point needs, in its order: the first null one fails with "<name> is null"
+struct NamedPtr {
+    const void* p;
+    const char* name;
+};
+int check_not_null(std::initializer_list<NamedPtr> need) {
+    for (const NamedPtr& a : need)
+        if (!a.p) return fail(DH_E_ARG, std::string(a.name) + " is null");
+    return DH_OK;
+}
+
+// The _dev entry points' body: the checks, then x [S][13] -> records and penalties in the
+// context's scratch (each set's spot and rate from its market row), then `launch`.  R brings the
+// markets and results; its scratch pointers are set here (extra only where the caller gave none).
+int rows_request_dev(dh_ctx* ctx, const dh_surface* s, std::initializer_list<NamedPtr> need,
+                     const double* d_x, const double* d_spot, const double* d_rate, GradRows R,
+                     Scratch kind, RowsLaunch launch, int N, double L, void* stream) {
+    int rc = check_loss_grad_rows(ctx, s, R.S, N, L);
+    if (rc) return rc;
+    rc = check_not_null(need);
+    if (rc) return rc;
+    DeviceScope dev_scope(ctx->device);
+    if (dev_scope.rc) return dev_scope.rc;
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    // grow-only: a request no larger than an earlier one on this context allocates nothing
+    HIP_TRY(ctx->pg_scratch.reserve(grad_scratch_bytes(R.S, s->M, kind)));
+    const GradScratch c = carve_grad_scratch(ctx->pg_scratch.ptr, R.S, s->M);
+    R.rec = c.rec, R.pen = c.pen, R.planes = c.planes;
+    if (!R.extra) R.extra = c.extra;
+    hipLaunchKernelGGL(x_records_rows_kernel, dim3((unsigned)((R.S + 255) / 256)), dim3(256), 0, st,
+                       d_x, R.S, d_spot, d_rate, R.row, c.rec, c.pen);
+    HIP_TRY(hipGetLastError());
+    return launch(ctx, s, R, N, L, st);
+}
+
+// An entry point's arrays, the host's or as rows_round_trip staged them on the device: x [S][13],
+// mkt [B][M] (prices, or vols), spot [B], rate [B], row [S] in; f [S], g [S][13], bad [S] and the
+// objective's extra (the vols as used [S][M] or null, or H [S][13][13]) out.  wgt [B][M] and div
+// [S] are what `prep` made, on the device only (null without).
+struct RowsIo {
+    const double *x, *mkt, *wgt, *div, *spot, *rate;
+    const int32_t* row;
+    double *f, *g;
+    int32_t* bad;
+    double* extra;
+};
+
+// The host entry points' round trip: the checks in the order below, the objective's own host
+// preparation (`prep(w, dv)` fills the weights [B][M] and divisors [S] it wants uploaded, or leaves
+// them empty), the uploads, the _dev form (`dev`), the downloads, synchronise.  w and dv are
+// pageable and declared ahead of the guard: every error return drains the stream before they go.
+template <typename Prep, typename Dev>
+int rows_round_trip(dh_ctx* ctx, const dh_surface* s, std::initializer_list<NamedPtr> need,
+                    const RowsIo& h, int S, int B, size_t n_extra, int N, double L, Prep&& prep,
+                    Dev&& dev) {
+    int rc = check_loss_grad_rows(ctx, s, S, N, L);
+    if (rc) return rc;
+    rc = check_not_null(need);
+    if (rc) return rc;
+    rc = check_rows(h.row, S, B);
+    if (rc) return rc;
+    rc = check_spot_rate(h.spot, h.rate, B);
+    if (rc) return rc;
+    std::vector<double> w, dv;
+    rc = prep(w, dv);
+    if (rc) return rc;
+    DeviceScope dev_scope(ctx->device);
+    if (dev_scope.rc) return dev_scope.rc;
+    constexpr int kN = kPlanes - 1;
+    const size_t xb = (size_t)S * kN * 8, mb = (size_t)B * s->M * 8, ne = h.extra ? n_extra : 0;
+    hipStream_t st = ctx->stream;
+    DrainOnError drain{st};
+    // x [S][13], then f [S], g [S][13], div [S], spot [B], rate [B], extra [ne], bad [S] (int32)
+    HIP_TRY(ctx->pg_io.reserve(2 * xb + (size_t)S * 20 + (size_t)B * 16 + ne * 8));
+    HIP_TRY(ctx->rows_mkt.reserve(mb));
+    if (!w.empty()) HIP_TRY(ctx->rows_wgt.reserve(mb));
+    HIP_TRY(ctx->rows_row.reserve((size_t)S * 4));
+    double* d_x = (double*)ctx->pg_io.ptr;
+    double* d_f = d_x + (size_t)S * kN;
+    double* d_g = d_f + S;
+    double* d_div = d_g + (size_t)S * kN;
+    double* d_spot = d_div + S;
+    double* d_rate = d_spot + B;
+    double* d_extra = d_rate + B;
+    int32_t* d_bad = (int32_t*)(d_extra + ne);
+    HIP_TRY(hipMemcpyAsync(d_x, h.x, xb, hipMemcpyHostToDevice, st));
+    if (!dv.empty())
+        HIP_TRY(hipMemcpyAsync(d_div, dv.data(), (size_t)S * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_spot, h.spot, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_rate, h.rate, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->rows_mkt.ptr, h.mkt, mb, hipMemcpyHostToDevice, st));
+    if (!w.empty())
+        HIP_TRY(hipMemcpyAsync(ctx->rows_wgt.ptr, w.data(), mb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->rows_row.ptr, h.row, (size_t)S * 4, hipMemcpyHostToDevice, st));
+    rc = dev(RowsIo{d_x, (const double*)ctx->rows_mkt.ptr,
+                    w.empty() ? nullptr : (const double*)ctx->rows_wgt.ptr,
+                    dv.empty() ? nullptr : d_div, d_spot, d_rate, (const int32_t*)ctx->rows_row.ptr,
+                    d_f, d_g, d_bad, ne ? d_extra : nullptr},
+             st);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(h.f, d_f, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h.g, d_g, xb, hipMemcpyDeviceToHost, st));
+    if (ne) HIP_TRY(hipMemcpyAsync(h.extra, d_extra, ne * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h.bad, d_bad, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    drain.armed = false;
+    return DH_OK;
+}
+
+// the price and Gauss-Newton objectives prepare nothing on the host
+inline int no_prep(std::vector<double>&, std::vector<double>&) { return DH_OK; }
 
 }  // namespace dhpg
 
@@ -718,17 +865,15 @@ extern "C" int dh_surface_loss_grad_dev(dh_ctx* ctx, const dh_surface* s, const 
     if (dev_scope.rc) return dev_scope.rc;
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     // grow-only: a request no larger than an earlier one on this context allocates nothing
-    HIP_TRY(ctx->pg_scratch.reserve(dhpg::loss_grad_scratch(S, s->M)));
-    double* d_rec = (double*)ctx->pg_scratch.ptr;
-    double* d_pen = d_rec + (size_t)S * DH_PARAM_STRIDE;
-    double* d_planes = d_pen + S;
+    HIP_TRY(ctx->pg_scratch.reserve(dhpg::grad_scratch_bytes(S, s->M, dhpg::Scratch::kPrice)));
+    const dhpg::GradScratch R = dhpg::carve_grad_scratch(ctx->pg_scratch.ptr, S, s->M);
     hipLaunchKernelGGL(x_records_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, d_x,
-                       S, S0, r, d_rec, d_pen);
+                       S, S0, r, R.rec, R.pen);
     HIP_TRY(hipGetLastError());
-    rc = dhpg::launch_param_grad(ctx, dhpg::surface_args(s, d_rec, S, N, L, d_planes), S, st);
+    rc = dhpg::launch_param_grad(ctx, dhpg::surface_args(s, R.rec, S, N, L, R.planes), S, st);
     if (rc) return rc;
     hipLaunchKernelGGL(dhpg::loss_grad_kernel, dim3(rows_grid(S)), dim3(kBlockRows), 0, st,
-                       (const double*)d_planes, (const double*)d_rec, (const double*)d_pen,
+                       (const double*)R.planes, (const double*)R.rec, (const double*)R.pen,
                        (const double*)s->mkt, (const int*)s->perm, s->M, (int64_t)S, d_f, d_g,
                        (int*)d_bad);
     HIP_TRY(hipGetLastError());
@@ -770,80 +915,31 @@ extern "C" int dh_surface_loss_grad_rows_dev(dh_ctx* ctx, const dh_surface* s, c
                                              const double* d_rate, const int32_t* d_row, int S,
                                              int N, double L, double* d_f, double* d_g,
                                              int32_t* d_bad, void* stream) {
-    int rc = dhpg::check_loss_grad_rows(ctx, s, S, N, L);
-    if (rc) return rc;
-    if (!d_x) return fail(DH_E_ARG, "x is null");
-    if (!d_mkt) return fail(DH_E_ARG, "mkt is null");
-    if (!d_spot) return fail(DH_E_ARG, "spot is null");
-    if (!d_rate) return fail(DH_E_ARG, "rate is null");
-    if (!d_row) return fail(DH_E_ARG, "row is null");
-    if (!d_f) return fail(DH_E_ARG, "f is null");
-    if (!d_g) return fail(DH_E_ARG, "g is null");
-    if (!d_bad) return fail(DH_E_ARG, "bad is null");
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    // dh_surface_loss_grad_dev's scratch and layout: records, penalties, planes
-    HIP_TRY(ctx->pg_scratch.reserve(dhpg::loss_grad_scratch(S, s->M)));
-    double* d_rec = (double*)ctx->pg_scratch.ptr;
-    double* d_pen = d_rec + (size_t)S * DH_PARAM_STRIDE;
-    double* d_planes = d_pen + S;
-    hipLaunchKernelGGL(dhpg::x_records_rows_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256),
-                       0, st, d_x, S, d_spot, d_rate, (const int*)d_row, d_rec, d_pen);
-    HIP_TRY(hipGetLastError());
-    return dhpg::loss_grad_rows_launch(ctx, s, d_rec, d_pen, d_mkt, (const int*)d_row, S, N, L,
-                                       d_planes, d_f, d_g, (int*)d_bad, st, nullptr);
+    dhpg::GradRows R{};
+    R.mkt = d_mkt;
+    R.row = (const int*)d_row;
+    R.f = d_f;
+    R.g = d_g;
+    R.bad = (int*)d_bad;
+    R.S = S;
+    return dhpg::rows_request_dev(ctx, s,
+                                  {{d_x, "x"}, {d_mkt, "mkt"}, {d_spot, "spot"}, {d_rate, "rate"},
+                                   {d_row, "row"}, {d_f, "f"}, {d_g, "g"}, {d_bad, "bad"}},
+                                  d_x, d_spot, d_rate, R, dhpg::Scratch::kPrice,
+                                  dhpg::loss_grad_rows_launch, N, L, stream);
 }
 
 extern "C" int dh_surface_loss_grad_rows(dh_ctx* ctx, const dh_surface* s, const double* x,
                                          const double* mkt, const double* spot,
                                          const double* rate, const int32_t* row, int S, int B,
                                          int N, double L, double* f, double* g, int32_t* bad) {
-    int rc = dhpg::check_loss_grad_rows(ctx, s, S, N, L);
-    if (rc) return rc;
-    if (!x) return fail(DH_E_ARG, "x is null");
-    if (!mkt) return fail(DH_E_ARG, "mkt is null");
-    if (!spot) return fail(DH_E_ARG, "spot is null");
-    if (!rate) return fail(DH_E_ARG, "rate is null");
-    if (!row) return fail(DH_E_ARG, "row is null");
-    if (!f) return fail(DH_E_ARG, "f is null");
-    if (!g) return fail(DH_E_ARG, "g is null");
-    if (!bad) return fail(DH_E_ARG, "bad is null");
-    rc = check_rows(row, S, B);
-    if (rc) return rc;
-    for (int b = 0; b < B; ++b) {
-        if (!std::isfinite(spot[b]) || !(spot[b] > 0.0))
-            return fail(DH_E_ARG, "spot " + std::to_string(b) + " is not finite or not > 0");
-        if (!std::isfinite(rate[b]))
-            return fail(DH_E_ARG, "rate " + std::to_string(b) + " is not finite");
-    }
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.rc) return dev_scope.rc;
-    constexpr int kN = dhpg::kPlanes - 1;
-    const size_t xb = (size_t)S * kN * 8, mb = (size_t)B * s->M * 8;
-    hipStream_t st = ctx->stream;
-    // x [S][13], then f [S], g [S][13], spot [B], rate [B], bad [S]
-    HIP_TRY(ctx->pg_io.reserve(2 * xb + (size_t)S * 16 + (size_t)B * 16));
-    HIP_TRY(ctx->rows_mkt.reserve(mb));
-    HIP_TRY(ctx->rows_row.reserve((size_t)S * 4));
-    double* d_x = (double*)ctx->pg_io.ptr;
-    double* d_f = d_x + (size_t)S * kN;
-    double* d_g = d_f + S;
-    double* d_spot = d_g + (size_t)S * kN;
-    double* d_rate = d_spot + B;
-    int32_t* d_bad = (int32_t*)(d_rate + B);
-    HIP_TRY(hipMemcpyAsync(d_x, x, xb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_spot, spot, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_rate, rate, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->rows_mkt.ptr, mkt, mb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->rows_row.ptr, row, (size_t)S * 4, hipMemcpyHostToDevice, st));
-    rc = dh_surface_loss_grad_rows_dev(ctx, s, d_x, (const double*)ctx->rows_mkt.ptr, d_spot,
-                                       d_rate, (const int32_t*)ctx->rows_row.ptr, S, N, L, d_f,
-                                       d_g, d_bad, st);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f, d_f, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(g, d_g, xb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(bad, d_bad, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DH_OK;
+    return dhpg::rows_round_trip(
+        ctx, s,
+        {{x, "x"}, {mkt, "mkt"}, {spot, "spot"}, {rate, "rate"}, {row, "row"}, {f, "f"}, {g, "g"},
+         {bad, "bad"}},
+        dhpg::RowsIo{x, mkt, nullptr, nullptr, spot, rate, row, f, g, bad, nullptr}, S, B, 0, N, L,
+        dhpg::no_prep, [&](const dhpg::RowsIo& d, hipStream_t st) {
+            return dh_surface_loss_grad_rows_dev(ctx, s, d.x, d.mkt, d.spot, d.rate, d.row, S, N,
+                                                 L, d.f, d.g, d.bad, st);
+        });
 }

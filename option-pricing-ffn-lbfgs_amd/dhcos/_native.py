@@ -1082,6 +1082,20 @@ class Surface(_Handle):
         _check(load().dh_surface_loss_rows_dev(self.ctx.handle, self._h, d_prices, d_mkt, d_row,
                                                int(S), d_sse, d_bad, _addr(stream)))
 
+    def _calibrate_batch(self, symbol, rows_first, mkt, weights, spots, rates, x0s, market_of, N, L,
+                         maxiter, maxfun, maxls, chunk, ftol, gtol, ctx):
+        """The five calibrate_*_batch* methods: lb_batch_args, and with rows_first iv_rows (mkt
+        holds vols and the weight rows follow it in the export's arguments), then _lbfgs."""
+        mkt, spots, rates, x0s, mof = lb_batch_args(self.M, mkt, spots, rates, x0s, market_of)
+        rows = (_ptr(mkt),)
+        if rows_first:
+            mkt, w = iv_rows(self.M, mkt, weights)
+            rows = (_ptr(mkt), _ptr(w))
+        B, S = mkt.shape[0], x0s.shape[0]
+        return _lbfgs(symbol, ctx or self.ctx, self, S,
+                      (*rows, _ptr(spots), _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p), S, int(N),
+                       float(L)), maxiter, maxfun, maxls, chunk, ftol, gtol)
+
     def calibrate_lbfgs_batch(self, mkt, spots, rates, x0s, market_of, N=128, L=10.0, *,
                               maxiter=300, maxfun=15000, maxls=20, ftol=1e-9, gtol=1e-6, chunk=8,
                               ctx=None):
@@ -1089,11 +1103,9 @@ class Surface(_Handle):
         (dh_calibrate_lbfgs_batch): row i of x0s [S, 13] fits market market_of[i] -- market
         prices mkt[b] of mkt [B, M], spot spots[b], rate rates[b].
         -> (list of LbResult, number of iterations enqueued)."""
-        mkt, spots, rates, x0s, mof = lb_batch_args(self.M, mkt, spots, rates, x0s, market_of)
-        B, S = mkt.shape[0], x0s.shape[0]
-        return _lbfgs("dh_calibrate_lbfgs_batch", ctx or self.ctx, self, S,
-                      (_ptr(mkt), _ptr(spots), _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p), S,
-                       int(N), float(L)), maxiter, maxfun, maxls, chunk, ftol, gtol)
+        return self._calibrate_batch(
+            "dh_calibrate_lbfgs_batch", False, mkt, None, spots, rates, x0s,
+            market_of, N, L, maxiter, maxfun, maxls, chunk, ftol, gtol, ctx)
 
     def loss_terms_iv_rows(self, params, mkt_iv, row, N=128, L=10.0, weights=None,
                            want_prices=False, want_iv=False):
@@ -1136,14 +1148,9 @@ class Surface(_Handle):
         [S, 13] fits the vols mkt_iv[b] of market b = market_of[i] under weights[b] (weights
         [B, M], [M] or None for all 1), spot spots[b], rate rates[b].
         -> (list of LbResult, number of iterations enqueued)."""
-        mkt_iv, spots, rates, x0s, mof = lb_batch_args(self.M, mkt_iv, spots, rates, x0s,
-                                                       market_of)
-        mkt_iv, w = iv_rows(self.M, mkt_iv, weights)
-        B, S = mkt_iv.shape[0], x0s.shape[0]
-        return _lbfgs("dh_calibrate_lbfgs_batch_iv", ctx or self.ctx, self, S,
-                      (_ptr(mkt_iv), _ptr(w), _ptr(spots), _ptr(rates), B, _ptr(x0s),
-                       _ptr(mof, _i32p), S, int(N), float(L)),
-                      maxiter, maxfun, maxls, chunk, ftol, gtol)
+        return self._calibrate_batch(
+            "dh_calibrate_lbfgs_batch_iv", True, mkt_iv, weights, spots, rates, x0s,
+            market_of, N, L, maxiter, maxfun, maxls, chunk, ftol, gtol, ctx)
 
     def fg(self, X0, S0, r, N=128, L=10.0, model=None):
         """dh_surface_fg: (f [S], g [S, 13], low [S]) of one FD request per row of X0 [S, 13].
@@ -1278,21 +1285,34 @@ class Surface(_Handle):
                                                float(S0), float(r), int(N), float(L), _addr(d_f),
                                                _addr(d_g), _addr(d_bad), _addr(stream)))
 
-    def loss_grad_rows(self, X, mkt, spots, rates, row, N=128, L=10.0):
-        """dh_surface_loss_grad_rows: loss_grad against a market row per set -- row s of X [S, 13]
-        under spots[row[s]] and rates[row[s]] against mkt[row[s]] of mkt [B, M] (the surface's
-        option order) -> (f [S], g [S, 13], bad [S]).  The surface needs no market prices."""
+    def _grad_rows_args(self, X, mkt, spots, rates, row, wgt=None, mkt_name="mkt"):
+        """The arguments of the three analytic *_rows methods as contiguous arrays, shapes checked
+        -> (X [S, 13], mkt [B, M], spots [B], rates [B], row [S] int32, wgt [B, M] or None, S, B)
+        and the outputs every one of them returns: f [S], g [S, 13], bad [S] int32."""
         X = _f64(X).reshape(-1, 13)
         S = X.shape[0]
         mkt = self._market_rows(mkt)
         B = mkt.shape[0]
+        w = None
+        if wgt is not None:
+            w = _f64(wgt)
+            if w.shape != mkt.shape:
+                raise ValueError(f"wgt must be {mkt.shape}, got {w.shape}")
         spots, rates = _f64(spots).reshape(-1), _f64(rates).reshape(-1)
         if spots.size != B or rates.size != B:
-            raise ValueError("mkt, spots and rates differ in length")
+            raise ValueError(f"{mkt_name}, spots and rates differ in length")
         row = np.ascontiguousarray(row, dtype=np.int32).reshape(-1)
         if row.size != S:
             raise ValueError("X and row differ in length")
-        f, g, bad = np.empty(S), np.empty((S, 13)), np.empty(S, dtype=np.int32)
+        return (X, mkt, spots, rates, row, w, S, B,
+                np.empty(S), np.empty((S, 13)), np.empty(S, dtype=np.int32))
+
+    def loss_grad_rows(self, X, mkt, spots, rates, row, N=128, L=10.0):
+        """dh_surface_loss_grad_rows: loss_grad against a market row per set -- row s of X [S, 13]
+        under spots[row[s]] and rates[row[s]] against mkt[row[s]] of mkt [B, M] (the surface's
+        option order) -> (f [S], g [S, 13], bad [S]).  The surface needs no market prices."""
+        X, mkt, spots, rates, row, _, S, B, f, g, bad = self._grad_rows_args(
+            X, mkt, spots, rates, row)
         with self.ctx._lock:
             _check(load().dh_surface_loss_grad_rows(
                 self.ctx.handle, self._h, _addr(X, S), _addr(mkt, B), _addr(spots, B),
@@ -1316,27 +1336,16 @@ class Surface(_Handle):
         """calibrate_lbfgs_batch with the analytic gradient (dh_calibrate_lbfgs_batch_grad): one
         loss evaluation per request (n_calls == nfev), N <= PARAM_GRAD_MAX_N.
         -> (list of LbResult, number of iterations enqueued)."""
-        mkt, spots, rates, x0s, mof = lb_batch_args(self.M, mkt, spots, rates, x0s, market_of)
-        B, S = mkt.shape[0], x0s.shape[0]
-        return _lbfgs("dh_calibrate_lbfgs_batch_grad", ctx or self.ctx, self, S,
-                      (_ptr(mkt), _ptr(spots), _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p), S,
-                       int(N), float(L)), maxiter, maxfun, maxls, chunk, ftol, gtol)
+        return self._calibrate_batch(
+            "dh_calibrate_lbfgs_batch_grad", False, mkt, None, spots, rates, x0s,
+            market_of, N, L, maxiter, maxfun, maxls, chunk, ftol, gtol, ctx)
 
     def gauss_newton_rows(self, X, mkt, spots, rates, row, N=128, L=10.0):
         """dh_surface_gauss_newton_rows: loss_grad_rows with the Gauss-Newton Hessian of the price
         part of the loss in the optimiser's x -> (f [S], g [S, 13], bad [S], H [S, 13, 13]); f, g
         and bad are loss_grad_rows's bits, H is exactly symmetric, and an invalid set has H = 0."""
-        X = _f64(X).reshape(-1, 13)
-        S = X.shape[0]
-        mkt = self._market_rows(mkt)
-        B = mkt.shape[0]
-        spots, rates = _f64(spots).reshape(-1), _f64(rates).reshape(-1)
-        if spots.size != B or rates.size != B:
-            raise ValueError("mkt, spots and rates differ in length")
-        row = np.ascontiguousarray(row, dtype=np.int32).reshape(-1)
-        if row.size != S:
-            raise ValueError("X and row differ in length")
-        f, g, bad = np.empty(S), np.empty((S, 13)), np.empty(S, dtype=np.int32)
+        X, mkt, spots, rates, row, _, S, B, f, g, bad = self._grad_rows_args(
+            X, mkt, spots, rates, row)
         H = np.empty((S, 13, 13))
         with self.ctx._lock:
             _check(load().dh_surface_gauss_newton_rows(
@@ -1361,11 +1370,9 @@ class Surface(_Handle):
         Gauss-Newton Hessian (dh_calibrate_lm_batch): one request per iteration (n_calls == nfev),
         nit accepted steps, task an LM_* code, N <= PARAM_GRAD_MAX_N.
         -> (list of LbResult, number of iterations enqueued)."""
-        mkt, spots, rates, x0s, mof = lb_batch_args(self.M, mkt, spots, rates, x0s, market_of)
-        B, S = mkt.shape[0], x0s.shape[0]
-        return _lbfgs("dh_calibrate_lm_batch", ctx or self.ctx, self, S,
-                      (_ptr(mkt), _ptr(spots), _ptr(rates), B, _ptr(x0s), _ptr(mof, _i32p), S,
-                       int(N), float(L)), maxiter, maxfun, 20, chunk, ftol, gtol)
+        return self._calibrate_batch(
+            "dh_calibrate_lm_batch", False, mkt, None, spots, rates, x0s,
+            market_of, N, L, maxiter, maxfun, 20, chunk, ftol, gtol, ctx)
 
     def iv_grad_rows_dev(self, d_planes: int, d_params: int, d_pen: int, d_mkt_iv: int, d_wgt: int,
                          d_row: int, d_div: int, S: int, d_f: int, d_g: int, d_bad: int,
@@ -1385,22 +1392,8 @@ class Surface(_Handle):
         of X [S, 13] under spots[row[s]] and rates[row[s]] against the vols mkt_iv[row[s]] under
         wgt[row[s]] (mkt_iv [B, M]; wgt [B, M] or None for all 1)
         -> (f [S], g [S, 13], bad [S], iv [S, M] the vols as used)."""
-        X = _f64(X).reshape(-1, 13)
-        S = X.shape[0]
-        mkt_iv = self._market_rows(mkt_iv)
-        B = mkt_iv.shape[0]
-        w = None
-        if wgt is not None:
-            w = _f64(wgt)
-            if w.shape != mkt_iv.shape:
-                raise ValueError(f"wgt must be {mkt_iv.shape}, got {w.shape}")
-        spots, rates = _f64(spots).reshape(-1), _f64(rates).reshape(-1)
-        if spots.size != B or rates.size != B:
-            raise ValueError("mkt_iv, spots and rates differ in length")
-        row = np.ascontiguousarray(row, dtype=np.int32).reshape(-1)
-        if row.size != S:
-            raise ValueError("X and row differ in length")
-        f, g, bad = np.empty(S), np.empty((S, 13)), np.empty(S, dtype=np.int32)
+        X, mkt_iv, spots, rates, row, w, S, B, f, g, bad = self._grad_rows_args(
+            X, mkt_iv, spots, rates, row, wgt, "mkt_iv")
         iv = np.empty((S, self.M))
         with self.ctx._lock:
             _check(load().dh_surface_loss_iv_grad_rows(
@@ -1426,14 +1419,9 @@ class Surface(_Handle):
         """calibrate_lbfgs_batch_iv with the vol objective's exact gradient
         (dh_calibrate_lbfgs_batch_iv_grad): one loss evaluation per request (n_calls == nfev), N <=
         PARAM_GRAD_MAX_N.  -> (list of LbResult, number of iterations enqueued)."""
-        mkt_iv, spots, rates, x0s, mof = lb_batch_args(self.M, mkt_iv, spots, rates, x0s,
-                                                       market_of)
-        mkt_iv, w = iv_rows(self.M, mkt_iv, weights)
-        B, S = mkt_iv.shape[0], x0s.shape[0]
-        return _lbfgs("dh_calibrate_lbfgs_batch_iv_grad", ctx or self.ctx, self, S,
-                      (_ptr(mkt_iv), _ptr(w), _ptr(spots), _ptr(rates), B, _ptr(x0s),
-                       _ptr(mof, _i32p), S, int(N), float(L)),
-                      maxiter, maxfun, maxls, chunk, ftol, gtol)
+        return self._calibrate_batch(
+            "dh_calibrate_lbfgs_batch_iv_grad", True, mkt_iv, weights, spots, rates, x0s,
+            market_of, N, L, maxiter, maxfun, maxls, chunk, ftol, gtol, ctx)
 
     def price_dev(self, d_params: int, P: int, d_out: int, N=128, L=10.0, stream: int = 0):
         _check(load().dh_surface_price_dev(self.ctx.handle, self._h, d_params, int(P), int(N),
