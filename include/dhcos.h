@@ -394,6 +394,36 @@ int dh_surface_greeks_dev(dh_ctx* ctx, const dh_surface* s, const double* d_para
 int dh_greeks_pairs(dh_ctx* ctx, const double* params, const double* K, const double* T,
                     const int8_t* is_call, int64_t n, int N, double L, double* out);
 
+/* ---- the full Greeks: maturity, rate, dual gamma, local variance (csrc/dh_greeks_full.h,
+ *      DESIGN.md 3.24) ------------------------------------------------------------------------- */
+/* The six planes above, bit for bit, and four more from the same pass, again partial derivatives of
+ * the series at FIXED [a, b] (fixed u_k) and fixed absolute strike:
+ *     DH_GREEK_DPRICE_DT   d / dT = -r price + e^{-rT} sum'_k Re(w_k G_k) V_k, G = d log phi / d tau
+ *                          (theta, the calendar decay per year, is its negative)
+ *     DH_GREEK_RHO         d / dr = -T price + e^{-rT} sum'_k (-u_k T Im w_k) V_k
+ *                          (d / dq = -(rho + T price))
+ *     DH_GREEK_DUAL_GAMMA  d2 / dK^2: V_k -> (2 / (b - a)) cos(u_k (xK - a)) / K; K^2 dual_gamma =
+ *                          S0^2 gamma; e^{rT} dual_gamma is the risk-neutral density of S_T at K
+ *     DH_GREEK_LOCAL_VAR   Dupire's local variance (with jumps: the model's Markovian projection),
+ *                          formed in fp64 without contraction from the planes of the same option as
+ *                              num = (dprice_dT + ((r - q) * K) * dual_delta) + q * price
+ *                              den = (0.5 * (K * K)) * dual_gamma
+ *                              local_var = num / den
+ *                          where those four planes are finite and den > 0, NaN otherwise; not
+ *                          clipped where negative.  The same for a call and a put.
+ * dprice_dT is not the total derivative in T: [a, b] moves with T and is held here, a difference
+ * of the size of the series' truncation error where the clamp is inactive.
+ * Arguments, refusals, layout (out[(g * P + p) * M + m], g < DH_N_GREEKS_FULL; pairs: out[g * n +
+ * i]) and reproducibility are those of the three calls above.                                    */
+enum { DH_GREEK_DPRICE_DT = 6, DH_GREEK_RHO = 7, DH_GREEK_DUAL_GAMMA = 8, DH_GREEK_LOCAL_VAR = 9,
+       DH_N_GREEKS_FULL = 10 };
+int dh_surface_greeks_full(dh_ctx* ctx, const dh_surface* s, const double* params, int64_t P,
+                           int N, double L, double* out);
+int dh_surface_greeks_full_dev(dh_ctx* ctx, const dh_surface* s, const double* d_params, int64_t P,
+                               int N, double L, double* d_out, void* stream);
+int dh_greeks_full_pairs(dh_ctx* ctx, const double* params, const double* K, const double* T,
+                         const int8_t* is_call, int64_t n, int N, double L, double* out);
+
 /* ---- analytic parameter sensitivities and the calibration gradient (csrc/dh_param_grad.h,
  * DESIGN.md 3.18) --------------------------------------------------------------------------- */
 /* Replaces nothing in the reference (it has no sensitivities and hands SciPy no gradient): it

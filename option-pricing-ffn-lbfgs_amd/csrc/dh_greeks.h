@@ -66,7 +66,7 @@ struct GreekArgs {
     int M;
     int N;
     double L;
-    double* out;            // [DH_N_GREEKS][plane]
+    double* out;            // [DH_N_GREEKS][plane] ([DH_N_GREEKS_FULL][plane] for the full build)
     int64_t plane;          // P * M (surface) or P (paired)
 };
 
@@ -347,11 +347,13 @@ int check_greeks(const dh_ctx* ctx, int64_t count, const char* count_name, int N
     return DH_OK;
 }
 
-}  // namespace dhgreeks
+// The three entry points' bodies, over the build that answers them: `launch` is launch_greeks or
+// the full build's (dh_greeks_full.h), `planes` the planes it writes.
+using LaunchFn = int (*)(dh_ctx*, GreekArgs, int64_t, hipStream_t);
 
-extern "C" int dh_surface_greeks_dev(dh_ctx* ctx, const dh_surface* s, const double* d_params,
-                                     int64_t P, int N, double L, double* d_out, void* stream) {
-    int rc = dhgreeks::check_greeks(ctx, P, "P", N, L);
+int surface_dev(dh_ctx* ctx, const dh_surface* s, const double* d_params, int64_t P, int N,
+                double L, double* d_out, void* stream, LaunchFn launch) {
+    int rc = check_greeks(ctx, P, "P", N, L);
     if (rc) return rc;
     if (!s) return fail(DH_E_ARG, "surface is null");
     if (!d_params) return fail(DH_E_ARG, "params is null");
@@ -359,7 +361,7 @@ extern "C" int dh_surface_greeks_dev(dh_ctx* ctx, const dh_surface* s, const dou
     if (s->M == 0) return DH_OK;
     DeviceScope dev_scope(ctx->device);
     if (dev_scope.rc) return dev_scope.rc;
-    dhgreeks::GreekArgs A{};
+    GreekArgs A{};
     A.prm = d_params;
     A.K = s->K;
     A.T = s->T;
@@ -375,12 +377,12 @@ extern "C" int dh_surface_greeks_dev(dh_ctx* ctx, const dh_surface* s, const dou
     A.L = L;
     A.out = d_out;
     A.plane = P * (int64_t)s->M;
-    return dhgreeks::launch_greeks(ctx, A, P, stream ? (hipStream_t)stream : ctx->stream);
+    return launch(ctx, A, P, stream ? (hipStream_t)stream : ctx->stream);
 }
 
-extern "C" int dh_surface_greeks(dh_ctx* ctx, const dh_surface* s, const double* params,
-                                 int64_t P, int N, double L, double* out) {
-    int rc = dhgreeks::check_greeks(ctx, P, "P", N, L);
+int surface_host(dh_ctx* ctx, const dh_surface* s, const double* params, int64_t P, int N,
+                 double L, double* out, LaunchFn launch, int planes) {
+    int rc = check_greeks(ctx, P, "P", N, L);
     if (rc) return rc;
     if (!s) return fail(DH_E_ARG, "surface is null");
     if (!params) return fail(DH_E_ARG, "params is null");
@@ -388,21 +390,22 @@ extern "C" int dh_surface_greeks(dh_ctx* ctx, const dh_surface* s, const double*
     if (s->M == 0) return DH_OK;
     DeviceScope dev_scope(ctx->device);
     if (dev_scope.rc) return dev_scope.rc;
-    const size_t pb = (size_t)P * DH_PARAM_STRIDE * 8, ob = (size_t)DH_N_GREEKS * P * s->M * 8;
+    const size_t pb = (size_t)P * DH_PARAM_STRIDE * 8, ob = (size_t)planes * P * s->M * 8;
     HIP_TRY(ctx->params.reserve(pb));
     HIP_TRY(ctx->out.reserve(ob));
     HIP_TRY(hipMemcpyAsync(ctx->params.ptr, params, pb, hipMemcpyHostToDevice, ctx->stream));
-    rc = dh_surface_greeks_dev(ctx, s, (const double*)ctx->params.ptr, P, N, L,
-                               (double*)ctx->out.ptr, ctx->stream);
+    rc = surface_dev(ctx, s, (const double*)ctx->params.ptr, P, N, L, (double*)ctx->out.ptr,
+                     ctx->stream, launch);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, ctx->out.ptr, ob, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return DH_OK;
 }
 
-extern "C" int dh_greeks_pairs(dh_ctx* ctx, const double* params, const double* K, const double* T,
-                               const int8_t* is_call, int64_t n, int N, double L, double* out) {
-    int rc = dhgreeks::check_greeks(ctx, n, "n", N, L);
+int pairs_host(dh_ctx* ctx, const double* params, const double* K, const double* T,
+               const int8_t* is_call, int64_t n, int N, double L, double* out, LaunchFn launch,
+               int planes) {
+    int rc = check_greeks(ctx, n, "n", N, L);
     if (rc) return rc;
     if (!params) return fail(DH_E_ARG, "params is null");
     if (!K) return fail(DH_E_ARG, "K is null");
@@ -414,7 +417,7 @@ extern "C" int dh_greeks_pairs(dh_ctx* ctx, const double* params, const double* 
     const size_t pb = (size_t)n * DH_PARAM_STRIDE * 8, vb = (size_t)n * 8;
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx->params.reserve(pb));
-    HIP_TRY(ctx->out.reserve(DH_N_GREEKS * vb));
+    HIP_TRY(ctx->out.reserve(planes * vb));
     HIP_TRY(ctx->aux0.reserve(vb));
     HIP_TRY(ctx->aux1.reserve(vb));
     HIP_TRY(ctx->aux2.reserve((size_t)n));
@@ -422,7 +425,7 @@ extern "C" int dh_greeks_pairs(dh_ctx* ctx, const double* params, const double* 
     HIP_TRY(hipMemcpyAsync(ctx->aux0.ptr, K, vb, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ctx->aux1.ptr, T, vb, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ctx->aux2.ptr, is_call, (size_t)n, hipMemcpyHostToDevice, st));
-    dhgreeks::GreekArgs A{};
+    GreekArgs A{};
     A.prm = (const double*)ctx->params.ptr;
     A.K = (const double*)ctx->aux0.ptr;
     A.T = (const double*)ctx->aux1.ptr;
@@ -433,9 +436,29 @@ extern "C" int dh_greeks_pairs(dh_ctx* ctx, const double* params, const double* 
     A.L = L;
     A.out = (double*)ctx->out.ptr;
     A.plane = n;
-    rc = dhgreeks::launch_greeks(ctx, A, n, st);
+    rc = launch(ctx, A, n, st);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, ctx->out.ptr, DH_N_GREEKS * vb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out, ctx->out.ptr, planes * vb, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return DH_OK;
+}
+
+}  // namespace dhgreeks
+
+extern "C" int dh_surface_greeks_dev(dh_ctx* ctx, const dh_surface* s, const double* d_params,
+                                     int64_t P, int N, double L, double* d_out, void* stream) {
+    return dhgreeks::surface_dev(ctx, s, d_params, P, N, L, d_out, stream,
+                                 dhgreeks::launch_greeks);
+}
+
+extern "C" int dh_surface_greeks(dh_ctx* ctx, const dh_surface* s, const double* params,
+                                 int64_t P, int N, double L, double* out) {
+    return dhgreeks::surface_host(ctx, s, params, P, N, L, out, dhgreeks::launch_greeks,
+                                  DH_N_GREEKS);
+}
+
+extern "C" int dh_greeks_pairs(dh_ctx* ctx, const double* params, const double* K, const double* T,
+                               const int8_t* is_call, int64_t n, int N, double L, double* out) {
+    return dhgreeks::pairs_host(ctx, params, K, T, is_call, n, N, L, out, dhgreeks::launch_greeks,
+                                DH_N_GREEKS);
 }

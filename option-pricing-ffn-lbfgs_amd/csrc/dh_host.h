@@ -180,6 +180,8 @@ struct dh_ctx {
     DevBuf lsm_state, lsm_cash, lsm_tau, lsm_part, lsm_fin, lsm_opts, lsm_disc, lsm_coef, lsm_out;    // the Greeks kernel (dh_greeks.h): the dynamic-LDS cap raised for it on this context's device
     // (bytes; 0: not yet)
     int greeks_lds = 0;
+    // the full Greeks kernel (dh_greeks_full.h): its dynamic-LDS cap likewise
+    int greeks_full_lds = 0;
     // the parameter-gradient kernel (dh_param_grad.h): its dynamic-LDS cap likewise; the records,
     // penalties and [14][S][M] planes of a loss_grad request; the host form's x, f, g and bad
     int param_grad_lds = 0;

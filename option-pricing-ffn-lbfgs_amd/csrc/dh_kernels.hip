@@ -2853,6 +2853,8 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
                              // variates): dh_host.h, dh_api.h
 #include "dh_lsm.h"          // American / Bermudan options by least-squares Monte Carlo: dh_mc.h
 #include "dh_greeks.h"       // analytic Greeks of the COS price: dh_host.h
+#include "dh_greeks_full.h"  // their full build (maturity, rate, dual gamma, local variance):
+                             // dh_greeks.h
 #include "dh_param_grad.h"   // analytic parameter sensitivities, loss + gradient, and the analytic
                              // rows request (GradRows, its scratch, epilogue and host path):
                              // dh_greeks.h, dh_loss_rows.h, dh_api.h

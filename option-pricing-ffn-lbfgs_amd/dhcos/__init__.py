@@ -21,6 +21,10 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
                                        every market from its prediction)
     greeks                            (new: analytic delta, gamma, dual delta and v0 vegas of the
                                        COS price, one pass; the module itself is dhcos/greeks.py)
+    greeks_full, local_vol            (new: greeks' planes and, from the same pass, the maturity,
+                                       rate and dividend sensitivities, the dual gamma / density
+                                       and Dupire's local volatility, on a (K, T) grid in one
+                                       launch; dhcos/greeks_full.py)
     parameter_sensitivities           (new: the price's analytic sensitivity to each of the 13 model
                                        parameters, one pass; DoubleHestonJumpCalibrator(...,
                                        gradient="analytic") fits with the exact loss gradient)
@@ -38,6 +42,7 @@ from .batch import BatchCalibrationResult, ParameterUncertainty, calibrate_batch
 from .montecarlo import MonteCarloResult, VarianceReducedResult, monte_carlo
 from .american import AmericanMonteCarloResult, american_monte_carlo
 from .greeks import Greeks, greeks
+from .greeks_full import FullGreeks, LocalVolSurface, greeks_full, local_vol
 from .param_sens import ParameterSensitivities, parameter_sensitivities
 from .ffn import FFNModel, fine_tune_ffn, price_features, train_ffn, train_ffn_on_generator
 from ._native import NativeError
@@ -47,6 +52,7 @@ __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
            "BatchCalibrationResult", "monte_carlo", "MonteCarloResult",
            "VarianceReducedResult",
            "american_monte_carlo", "AmericanMonteCarloResult", "greeks", "Greeks",
+           "greeks_full", "FullGreeks", "local_vol", "LocalVolSurface",
            "parameter_sensitivities", "ParameterSensitivities", "ParameterUncertainty",
            "FFNModel", "train_ffn", "train_ffn_on_generator", "fine_tune_ffn", "price_features"]
 __version__ = "0.1.0"

@@ -50,6 +50,9 @@ FFN_MAX_IN = 64                # DH_FFN_MAX_IN: features and prices per market a
 STAMPS_PER_BLOCK = 32          # kStamps of the DH_STAMPS build (csrc/dh_kernels.hip)
 # the planes of dh_surface_greeks / dh_greeks_pairs, in the order of the header's DH_GREEK_* enum
 GREEKS = ("price", "delta", "gamma", "dual_delta", "vega1", "vega2")
+# the planes of dh_surface_greeks_full / dh_greeks_full_pairs: GREEKS, then DH_GREEK_DPRICE_DT ...
+# DH_GREEK_LOCAL_VAR (DH_N_GREEKS_FULL planes)
+GREEKS_FULL = GREEKS + ("dprice_dT", "rho", "dual_gamma", "local_var")
 # the planes of dh_surface_param_sens / dh_param_sens_pairs: the price, then the record's thirteen
 # model parameters (DH_N_PARAM_SENS planes); the longest series they take (DH_PARAM_GRAD_MAX_N)
 PARAM_SENS = ("price", "v1_0", "kappa1", "theta1", "sigma1", "rho1", "v2_0", "kappa2", "theta2",
@@ -173,6 +176,10 @@ SIGNATURES = {
     "dh_surface_greeks": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp]),
     "dh_surface_greeks_dev": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp, _vp]),
     "dh_greeks_pairs": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _dbl, _vp]),
+    # ---- the full Greeks: maturity, rate, dual gamma, local variance
+    "dh_surface_greeks_full": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp]),
+    "dh_surface_greeks_full_dev": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp, _vp]),
+    "dh_greeks_full_pairs": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _dbl, _vp]),
     # ---- analytic parameter sensitivities, the loss and its gradient
     "dh_surface_param_sens": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp]),
     "dh_surface_param_sens_dev": (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _vp, _vp]),
@@ -561,6 +568,19 @@ class Context(_Handle):
         with self._lock:
             _check(load().dh_greeks_pairs(self._h, _addr(params, n), _addr(K, n), _addr(T, n),
                                           _addr(ic, n), n, int(N), float(L), _addr(out, n)))
+        return out
+
+    def greeks_full_pairs(self, params, K, T, is_call, N=128, L=10.0):
+        """dh_greeks_full_pairs: the planes GREEKS_FULL of option i under param record i
+        -> [10, n]."""
+        params = _records(params)
+        n = params.shape[0]
+        K, T = _f64(K).reshape(n), _f64(T).reshape(n)
+        ic = _flags(is_call, n)
+        out = np.empty((len(GREEKS_FULL), n))
+        with self._lock:
+            _check(load().dh_greeks_full_pairs(self._h, _addr(params, n), _addr(K, n), _addr(T, n),
+                                               _addr(ic, n), n, int(N), float(L), _addr(out, n)))
         return out
 
     def param_sens_pairs(self, params, K, T, is_call, N=128, L=10.0):
@@ -1245,6 +1265,24 @@ class Surface(_Handle):
         """dh_surface_greeks_dev: d_params [P, 16] in, d_out [6, P, M] out, enqueued on stream."""
         _check(load().dh_surface_greeks_dev(self.ctx.handle, self._h, _addr(d_params), int(P),
                                             int(N), float(L), _addr(d_out), _addr(stream)))
+
+    def greeks_full(self, params, N=128, L=10.0):
+        """dh_surface_greeks_full: the planes GREEKS_FULL (greeks' six, bit for bit, then
+        d price / dT, rho, dual gamma and Dupire's local variance) of every option under every
+        param row -> [10, P, M] (include/dhcos.h)."""
+        params = _records(params)
+        P = params.shape[0]
+        out = np.empty((len(GREEKS_FULL), P, self.M))
+        with self.ctx._lock:
+            _check(load().dh_surface_greeks_full(self.ctx.handle, self._h, _addr(params, P), P,
+                                                 int(N), float(L), out.ctypes.data))
+        return out
+
+    def greeks_full_dev(self, d_params: int, P: int, d_out: int, N=128, L=10.0, stream: int = 0):
+        """dh_surface_greeks_full_dev: d_params [P, 16] in, d_out [10, P, M] out, enqueued on
+        stream."""
+        _check(load().dh_surface_greeks_full_dev(self.ctx.handle, self._h, _addr(d_params), int(P),
+                                                 int(N), float(L), _addr(d_out), _addr(stream)))
 
     def param_sens(self, params, N=128, L=10.0):
         """dh_surface_param_sens: the planes PARAM_SENS (the price, then its sensitivity to each of
@@ -1949,7 +1987,7 @@ __all__ = [
     "LIB_PATH", "SIGNATURES", "NativeError", "load", "runtime_shared_with_torch", "device_count",
     "resolve_device", "default_context", "PARAM_STRIDE", "MAX_N", "MAX_N_PER_TERM",
     "STRIKE_ABSOLUTE", "STRIKE_PCT_SPOT", "PATH_AUTO", "PATH_SPLIT", "PATH_FUSED", "PATH_GEN",
-    "FG_SLOTS", "STAMPS_PER_BLOCK", "GREEKS", "PARAM_SENS", "PARAM_GRAD_MAX_N",
+    "FG_SLOTS", "STAMPS_PER_BLOCK", "GREEKS", "GREEKS_FULL", "PARAM_SENS", "PARAM_GRAD_MAX_N",
     "LM_MESSAGES", "Context", "Surface", "FgChannel", "pinned", "pinned_empty", "host_cache_trim",
     "LbOptions", "LbResult", "lb_batch_args", "iv_rows",
     "gen_draw", "GenDraw", "GEN_LOC_WORDS", "gen_locate", "gen_draw_located", "gen_sweep",

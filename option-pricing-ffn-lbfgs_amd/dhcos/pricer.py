@@ -156,6 +156,17 @@ class DoubleHeston:
                                        [resolve_call(self.option_type)], check_N(N))
         return Greeks.from_planes(out[:, 0])
 
+    def greeks_full(self, N=128):
+        """``FullGreeks`` of this instance's option as scalars: ``greeks(N)``'s six planes with the
+        same bits, and dprice_dT, rho, dual_gamma and Dupire's local_var (with theta, epsilon,
+        density and local_vol derived from them), partial derivatives at a fixed truncation range
+        (``dhcos.greeks_full``)."""
+        from .greeks import check_N
+        from .greeks_full import FullGreeks
+        out = self._ctx().greeks_full_pairs(self._record(), [float(self.K)], [float(self.T)],
+                                            [resolve_call(self.option_type)], check_N(N))
+        return FullGreeks.from_planes(out[:, 0], np.float64(self.T), np.float64(self.r))
+
     def parameter_sensitivities(self, N=128):
         """``ParameterSensitivities`` (the price and d price / d each of the 13 model parameters) of
         this instance's option as scalars: analytic partial derivatives of ``pricing(N)``'s COS
@@ -217,6 +228,19 @@ class DoubleHeston:
         rec, Kb, Tb, ic = _pair_args(params, S0, K, T, r, option_type, q)
         return Greeks.from_planes(
             _native.default_context(device).greeks_pairs(rec, Kb, Tb, ic, N, L))
+
+    @staticmethod
+    def greeks_full_batch(params, S0, K, T, r, option_type="C", N=128, q=0.0, L=10.0,
+                          device=None):
+        """``price_batch``'s arguments -> ``FullGreeks`` of ``[n]`` arrays: the ten planes of option
+        i under param set i, all in one launch (``dhcos.greeks_full``)."""
+        from .greeks import check_L, check_N
+        from .greeks_full import FullGreeks
+        N, L = check_N(N), check_L(L)
+        rec, Kb, Tb, ic = _pair_args(params, S0, K, T, r, option_type, q)
+        return FullGreeks.from_planes(
+            _native.default_context(device).greeks_full_pairs(rec, Kb, Tb, ic, N, L), Tb,
+            rec[:, 14].copy())
 
     @staticmethod
     def implied_vol_batch(params, S0, K, T, r, option_type="C", N=128, q=0.0, L=10.0,
