@@ -953,6 +953,51 @@ int dh_mc_paths_vr(dh_ctx* ctx, const double* params, int64_t P, int n_obs,
                    const int32_t* obs_steps, int64_t path0, int64_t n_paths, int steps_per_year,
                    uint64_t seed, int mirror, double* out);
 
+/* ---- Greeks of the path pricer from coupled paths (csrc/dh_mc_greeks.h) --- */
+/* Delta, gamma and the two v0 vegas of every option of dh_mc_price, with standard errors, from one
+ * walk.  Inputs are those of dh_mc_price, plus spot_bump = eps (relative, 0 < eps < 1) and
+ * v0_bump = b (relative, 0 < b < 1).  For a parameter record with spot S0:
+ *     h = eps S0,   u+- = 1 +- eps,   d_j = b v0_j.
+ * For path i and option o at its maturity step, the five payoffs are
+ *     y      the payoff of dh_mc_price on the base path's state;
+ *     y_S+-  the same payoff function on the base state with S, the running maximum, minimum and
+ *            sum each multiplied by u+- (barrier tests use u max < barrier and u min > barrier, the
+ *            Asian underlier is u sum / step): spot enters a path only as S = S0 exp(x), so this is
+ *            the path at spot S0 u+-;
+ *     y_j+-  the payoff on the path walked from v0_j +- d_j, with the same draws; the other factor
+ *            and the jumps are the base path's.
+ * The samples are
+ *     delta_i  = (y_S+ - y_S-) / (2 h),
+ *     gamma_i  = ((y_S+ - y) + (y_S- - y)) / (h h),
+ *     vega_j,i = (y_j+ - y_j-) / (2 d_j),  j = 1, 2   (per unit of variance, as dh_surface_greeks).
+ * For each of the five samples (price first), with disc = e^{-rT} and the sums over the n paths,
+ *     value = disc Sum / n,   stderr = disc sqrt(max(Sum2 - Sum Sum / n, 0) / (n (n - 1))),
+ * every sum in dh_mc_price's order (a xor butterfly per wave, the four waves as (w0 + w1) + (w2 +
+ * w3), chunks in increasing order, slots in slot order): no atomics, the same call gives the same
+ * bits, and the price plane and its stderr are dh_mc_price's bits.  A barrier's delta and gamma
+ * carry the paths that u+- moves across the barrier: they estimate the difference quotients at eps,
+ * not the derivatives.  Antithetic pairs and the control variate are not composed with these.   */
+enum dh_mc_greek {
+    DH_MC_GREEK_PRICE = 0, DH_MC_GREEK_DELTA, DH_MC_GREEK_GAMMA, DH_MC_GREEK_VEGA1,
+    DH_MC_GREEK_VEGA2, DH_MC_N_GREEKS
+};
+/* value[(p * n_options + j) * DH_MC_N_GREEKS + g], stderr_out laid out the same way.  Host arrays,
+ * synchronous.  DH_E_ARG, before any device work and naming the argument in dh_last_error():
+ * everything dh_mc_price refuses; spot_bump or v0_bump outside (0, 1) or not finite; a record with
+ * a v0 of 0, whose relative bump would be empty (v0_j - d_j > 0 always holds for b < 1).         */
+int dh_mc_greeks(dh_ctx* ctx, const double* params, int64_t P, const dh_mc_option* options,
+                 int n_options, int64_t n_paths, int steps_per_year, uint64_t seed,
+                 double spot_bump, double v0_bump, double* value, double* stderr_out);
+/* The same over device pointers (d_params [P][16] in, d_value / d_stderr [P][n_options][
+ * DH_MC_N_GREEKS] out; `options` stays a host array, copied when the call returns): two launches
+ * enqueued on `stream` (hipStream_t; NULL = the context's), no synchronisation, no allocation
+ * after warm-up.  The parameter values are the caller's promise (not readable here: a v0 of 0
+ * gives NaN vegas); the same bits as dh_mc_greeks.                                              */
+int dh_mc_greeks_dev(dh_ctx* ctx, const double* d_params, int64_t P, const dh_mc_option* options,
+                     int n_options, int64_t n_paths, int steps_per_year, uint64_t seed,
+                     double spot_bump, double v0_bump, double* d_value, double* d_stderr,
+                     void* stream);
+
 /* ---- American and Bermudan options by least-squares Monte Carlo (csrc/dh_lsm.h) */
 /* Early exercise on the paths of the pricer above, by the method of Longstaff and Schwartz (2001).
  * The exercise dates are the steps e, 2 e, 3 e, ... (e = exercise_every >= 1; the start value is

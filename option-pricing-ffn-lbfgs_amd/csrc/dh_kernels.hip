@@ -2851,6 +2851,7 @@ __global__ void loss_finalize_kernel(const double* __restrict__ sse, const int* 
 #include "dh_math_probe.h"   // the device math primitives one by one: dh_host.h
 #include "dh_mc.h"           // the Monte Carlo path pricer (includes dh_mc_vr.h, its control
                              // variates): dh_host.h, dh_api.h
+#include "dh_mc_greeks.h"    // its delta, gamma and v0 vegas from coupled paths: dh_mc.h
 #include "dh_lsm.h"          // American / Bermudan options by least-squares Monte Carlo: dh_mc.h
 #include "dh_greeks.h"       // analytic Greeks of the COS price: dh_host.h
 #include "dh_greeks_full.h"  // their full build (maturity, rate, dual gamma, local variance):

@@ -14,6 +14,8 @@ Drop-in host API for the hot path of zenthepen/Option-Pricing-FFN-LBFGS:
                                        covariance, standard errors and conditioning)
     monte_carlo                       (new: path pricing of European, Asian and barrier options,
                                        with antithetic pairs and COS-priced control variates)
+    monte_carlo_greeks                (new: their delta, gamma and v0 vegas with standard errors,
+                                       from coupled paths in one walk)
     american_monte_carlo              (new: American and Bermudan options by least-squares Monte Carlo)
     FFNModel, train_ffn,              (new: the warm-start network of the reference's documents --
     train_ffn_on_generator,            trained in PyTorch on the generator's output, evaluated by
@@ -39,7 +41,8 @@ from .pricer import DoubleHeston, implied_vol
 from .calibrator import CalibrationResult, DoubleHestonJumpCalibrator
 from .generator import generate_synthetic_calibrations
 from .batch import BatchCalibrationResult, ParameterUncertainty, calibrate_batch
-from .montecarlo import MonteCarloResult, VarianceReducedResult, monte_carlo
+from .montecarlo import (MonteCarloGreeks, MonteCarloResult, VarianceReducedResult, monte_carlo,
+                         monte_carlo_greeks)
 from .american import AmericanMonteCarloResult, american_monte_carlo
 from .greeks import Greeks, greeks
 from .greeks_full import FullGreeks, LocalVolSurface, greeks_full, local_vol
@@ -50,7 +53,7 @@ from ._native import NativeError
 __all__ = ["DoubleHeston", "DoubleHestonJumpCalibrator", "CalibrationResult",
            "generate_synthetic_calibrations", "implied_vol", "NativeError", "calibrate_batch",
            "BatchCalibrationResult", "monte_carlo", "MonteCarloResult",
-           "VarianceReducedResult",
+           "VarianceReducedResult", "monte_carlo_greeks", "MonteCarloGreeks",
            "american_monte_carlo", "AmericanMonteCarloResult", "greeks", "Greeks",
            "greeks_full", "FullGreeks", "local_vol", "LocalVolSurface",
            "parameter_sensitivities", "ParameterSensitivities", "ParameterUncertainty",

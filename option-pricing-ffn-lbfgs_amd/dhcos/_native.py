@@ -37,6 +37,8 @@ MC_MAX_OPTIONS = 64            # DH_MC_MAX_OPTIONS
 MC_POISSON_CAP = 16            # DH_MC_POISSON_CAP
 MC_VR_ANTITHETIC, MC_VR_CONTROL = 1, 2     # DH_MC_VR_*: the flags of dh_mc_price_vr
 MC_VR_COS_N, MC_VR_COS_L = 256, 10.0       # DH_MC_VR_COS_*: the COS series of the control means
+# the planes of dh_mc_greeks, in the order of the header's DH_MC_GREEK_* enum (DH_MC_N_GREEKS)
+MC_GREEKS = ("price", "delta", "gamma", "vega_v01", "vega_v02")
 LSM_MAX_OPTIONS = 16           # DH_LSM_MAX_OPTIONS
 LSM_BASIS = 10                 # DH_LSM_BASIS: regression terms
 LSM_MIN_ITM = 64               # DH_LSM_MIN_ITM: in-the-money paths a date needs to be fitted
@@ -263,6 +265,11 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "dh_mc_paths_vr": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _i64, _int, C.c_uint64, _int,
                               _vp]),
+    # ---- its delta, gamma and v0 vegas from coupled paths
+    "dh_mc_greeks": (_int, [_vp, _vp, _i64, _mco, _int, _i64, _int, C.c_uint64, _dbl, _dbl, _vp,
+                            _vp]),
+    "dh_mc_greeks_dev": (_int, [_vp, _vp, _i64, _mco, _int, _i64, _int, C.c_uint64, _dbl, _dbl,
+                                _vp, _vp, _vp]),
     # ---- American and Bermudan options by least-squares Monte Carlo
     "dh_lsm_price": (_int, [_vp, _vp, _i64, _lso, _int, _i64, _int, _int, C.c_uint64, _vp, _vp,
                             _vp, _vp, _vp, _vp]),
@@ -739,6 +746,37 @@ class Context(_Handle):
                                          int(steps_per_year), int(seed), 1 if mirror else 0,
                                          out.ctypes.data))
         return out
+
+    def mc_greeks(self, records, options, n_paths, steps_per_year, seed, spot_bump, v0_bump):
+        """dh_mc_greeks: records [P, 16], options an array of McOption -> (value, stderr), each
+        [P, n_options, len(MC_GREEKS)]."""
+        rec = _records(records)
+        P, n_opt = rec.shape[0], len(options)
+        out = np.empty((2, P, n_opt, len(MC_GREEKS)))
+        with self._lock:
+            _check(load().dh_mc_greeks(self._h, rec.ctypes.data, P, options, n_opt, int(n_paths),
+                                       int(steps_per_year), int(seed), float(spot_bump),
+                                       float(v0_bump), out[0].ctypes.data, out[1].ctypes.data))
+        return out[0], out[1]
+
+    def mc_greeks_dev(self, records, options, n_paths, steps_per_year, seed, spot_bump, v0_bump,
+                      stream=None):
+        """dh_mc_greeks_dev: records a contiguous float64 [P, 16] torch tensor on this context's
+        device -> (value, stderr) tensors [P, n_options, len(MC_GREEKS)], enqueued on ``stream``
+        (None: the context's own; the null stream cannot be named, as mc_price_dev) without
+        synchronisation."""
+        import torch
+        self._check_records_tensor("mc_greeks_dev", records)
+        P, n_opt = records.shape[0], len(options)
+        out = torch.empty((2, P, n_opt, len(MC_GREEKS)), dtype=torch.float64,
+                          device=records.device)
+        st = _stream_handle("mc_greeks_dev", stream)
+        with self._lock:
+            _check(load().dh_mc_greeks_dev(self._h, records.data_ptr(), P, options, n_opt,
+                                           int(n_paths), int(steps_per_year), int(seed),
+                                           float(spot_bump), float(v0_bump), out[0].data_ptr(),
+                                           out[1].data_ptr(), _addr(st)))
+        return out[0], out[1]
 
     def lsm_price(self, records, options, dates, n_paths, steps_per_year, exercise_every, seed,
                   policy=False):
@@ -1995,7 +2033,7 @@ __all__ = [
     "MATH_PROBE_FNS", "math_probe",
     "COMM_ID_BYTES", "Comm", "comm_id", "best_start",
     "McOption", "MC_KINDS", "MC_MAX_OPTIONS", "MC_POISSON_CAP",
-    "MC_VR_ANTITHETIC", "MC_VR_CONTROL", "MC_VR_COS_N", "MC_VR_COS_L",
+    "MC_VR_ANTITHETIC", "MC_VR_CONTROL", "MC_VR_COS_N", "MC_VR_COS_L", "MC_GREEKS",
     "LsmOption", "LSM_MAX_OPTIONS", "LSM_BASIS", "LSM_MIN_ITM", "LSM_SLOTS", "LSM_MAX_GIB",
     "FFN", "FFN_OUT", "FFN_TM", "FFN_MAX_HIDDEN", "FFN_MAX_WIDTH", "FFN_MAX_IN",
 ]

@@ -209,6 +209,80 @@ def monte_carlo(parameters, spot, risk_free, options, *, n_paths=1 << 20, steps_
                                  bool(antithetic), bool(control_variate))
 
 
+@dataclass
+class MonteCarloGreeks:
+    """``monte_carlo_greeks``: the price, delta, gamma and the two v0 vegas (per unit of variance,
+    as ``dhcos.greeks``) of every option, each with the standard error of its own paired samples:
+    ``[n_options]`` for one parameter set, ``[P, n_options]`` for ``P``.  ``price`` and
+    ``price_stderr`` are ``monte_carlo``'s bits.  delta and gamma are central differences in spot
+    at the relative step ``spot_bump``, the vegas in ``v0_j`` at the relative step ``v0_bump``: of a
+    barrier option they estimate the difference quotient at that step, not the derivative."""
+    price: np.ndarray
+    price_stderr: np.ndarray
+    delta: np.ndarray
+    delta_stderr: np.ndarray
+    gamma: np.ndarray
+    gamma_stderr: np.ndarray
+    vega_v01: np.ndarray
+    vega_v01_stderr: np.ndarray
+    vega_v02: np.ndarray
+    vega_v02_stderr: np.ndarray
+    n_paths: int
+    steps_per_year: int
+    seed: int
+    spot_bump: float
+    v0_bump: float
+
+    def confidence(self, z: float = 1.96):
+        """{name: (low, high)} = value -+ z stderr of each of the five."""
+        return {n: (getattr(self, n) - z * getattr(self, n + "_stderr"),
+                    getattr(self, n) + z * getattr(self, n + "_stderr"))
+                for n in _native.MC_GREEKS}
+
+
+def _check_bump(name, v):
+    v = float(v)
+    if not 0.0 < v < 1.0:                # NaN and the infinities fail both comparisons' chain
+        raise ValueError(f"{name}: a relative step inside (0, 1), got {v!r}")
+    return v
+
+
+def monte_carlo_greeks(parameters, spot, risk_free, options, *, n_paths=1 << 20,
+                       steps_per_year=64, seed=0, spot_bump=1e-2, v0_bump=5e-2,
+                       device=None) -> MonteCarloGreeks:
+    """Price, delta, gamma and the two v0 vegas of ``options`` with their standard errors, from one
+    walk of coupled paths on the GPU (dh_mc_greeks).
+
+    parameters, spot, risk_free, options, n_paths, steps_per_year, seed: as ``monte_carlo``, whose
+    price and standard error this call reproduces bit for bit.  spot_bump: the relative step
+    ``eps`` of the central differences in spot (the paths at ``spot (1 +- eps)`` are the base paths
+    scaled, no walk of their own); v0_bump: the relative step ``b`` of those in each ``v0_j`` (the
+    paths from ``v0_j (1 +- b)`` share every random number, the other factor and the jumps with the
+    base path); both inside (0, 1), and neither ``v0`` may be 0.  Antithetic pairs and the control
+    variate of ``monte_carlo`` are not composed with the Greeks."""
+    steps_per_year = _check_steps_per_year(steps_per_year)
+    seed = _check_seed(seed)
+    if int(n_paths) != n_paths or n_paths < 2:
+        raise ValueError(f"n_paths: a whole number >= 2, got {n_paths!r}")
+    spot_bump = _check_bump("spot_bump", spot_bump)
+    v0_bump = _check_bump("v0_bump", v0_bump)
+    rec, single = _records(parameters, spot, risk_free)
+    _check_records(rec, steps_per_year)
+    for k, name in ((0, "v1_0"), (5, "v2_0")):
+        if not (rec[:, k] != 0.0).all():
+            raise ValueError(f"{name} of set {int(np.argmin(rec[:, k] != 0.0))} is 0: its relative "
+                             f"bump v0_bump would be empty")
+    opts = _options(options, steps_per_year)
+    value, err = _native.default_context(device).mc_greeks(rec, opts, int(n_paths), steps_per_year,
+                                                           seed, spot_bump, v0_bump)
+    if single:
+        value, err = value[0], err[0]
+    planes = []
+    for g in range(len(_native.MC_GREEKS)):
+        planes += [np.ascontiguousarray(value[..., g]), np.ascontiguousarray(err[..., g])]
+    return MonteCarloGreeks(*planes, int(n_paths), steps_per_year, seed, spot_bump, v0_bump)
+
+
 def simulate_paths(parameters, spot, risk_free, obs_steps, *, n_paths, path0=0, steps_per_year=64,
                    seed=0, device=None, mirror=False) -> np.ndarray:
     """dh_mc_paths: ``S, v1, v2, running max, running min, running sum`` of paths ``path0 ..
@@ -242,5 +316,5 @@ def simulate_paths(parameters, spot, risk_free, obs_steps, *, n_paths, path0=0, 
     return out[0] if single else out
 
 
-__all__ = ["monte_carlo", "simulate_paths", "MonteCarloResult", "VarianceReducedResult", "KINDS",
-           "MAX_OPTIONS"]
+__all__ = ["monte_carlo", "monte_carlo_greeks", "simulate_paths", "MonteCarloResult",
+           "VarianceReducedResult", "MonteCarloGreeks", "KINDS", "MAX_OPTIONS"]

@@ -193,6 +193,25 @@ class DoubleHeston:
                           control_variate=control_variate)
         return np.float64(res.price[0]), np.float64(res.stderr[0])
 
+    def monte_carlo_greeks(self, n_paths=1 << 20, steps_per_year=64, seed=0, spot_bump=1e-2,
+                           v0_bump=5e-2):
+        """``MonteCarloGreeks`` (price, delta, gamma and the v0 vegas, each with its standard
+        error) of this instance's option as scalars, from one walk of coupled paths
+        (``dhcos.monte_carlo_greeks``; q must be 0, the simulated dynamics carry no dividend
+        yield)."""
+        from .montecarlo import monte_carlo_greeks
+        if self.q != 0.0:
+            raise ValueError("monte_carlo_greeks: the simulated dynamics have q = 0")
+        res = monte_carlo_greeks([getattr(self, f) for f in MODEL_FIELDS], self.S0, self.r,
+                                 [{"strike": self.K, "maturity": self.T,
+                                   "option_type": self.option_type}],
+                                 n_paths=n_paths, steps_per_year=steps_per_year, seed=seed,
+                                 spot_bump=spot_bump, v0_bump=v0_bump, device=self.device)
+        for name in _native.MC_GREEKS:
+            for field in (name, name + "_stderr"):
+                setattr(res, field, np.float64(getattr(res, field)[0]))
+        return res
+
     def american_monte_carlo(self, n_paths=1 << 17, steps_per_year=64, exercise_every=1, seed=0):
         """(price, stderr) of this instance's option with early exercise at every
         ``exercise_every``-th step, by least-squares Monte Carlo (``dhcos.american_monte_carlo``;
